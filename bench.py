@@ -1,7 +1,13 @@
 """Headline benchmark: Mpps classified (5-tuple -> rule verdict, both policy stages) @100k rules.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--packets 67108864]
+    python bench.py --full        # the same line plus parity stamp, CPU baseline, counter roofline
+    python bench.py --dump-outputs DIR   # the last timed step's outputs as DIR/<name>.npy
     python bench.py --config C5   # C3 + AddPolicyRuleAddress/DeletePolicyRuleAddress churn
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (`ms_per_step` = wall time
+of the timed region / steps); everything below that needs a run or a process of its own is done
+only with `--full`.
 
 C5 (BASELINE config 5): the C3 rule set with address updates interleaved with
 classification. A control thread applies `--churn-rate` ops/s (alternating add / delete of /32
@@ -15,7 +21,8 @@ the timed region) and, when counters are on, all-reduces the per-rule counters o
 end of the run (the only collective of the path). A step = one gpc_classify call
 over the whole per-GPU batch (two kernel launches without Services: egress stage, ingress stage).
 
-Rank 0 at N = 1 also (all after the timed region, none of it timed):
+With `--full`, rank 0 at N = 1 also (all outside the timed region, none of it timed; each leg can be
+switched off again with `--no-parity`, `--no-cpu-baseline`, `--no-traffic`):
   * parity: a 64k-packet strided sample of the timed batch and its device verdicts are checked
     packet for packet against the C oracle (oracle/ovs_cls.c over the ORACLE compiler's flows),
     which a spawned CPU process prepares while the GPU works -> "parity": {checked, mismatches};
@@ -23,7 +30,15 @@ Rank 0 at N = 1 also (all after the timed region, none of it timed):
   * roofline: the dominant kernel's measured L2<->fabric bytes per launch (rocprofv3 FETCH_SIZE x2 +
     WRITE_SIZE, separate child passes, MI355X_MICROARCH.md HBM section) / its mean duration from HIP
     events recorded around every launch of the timed region (gpc_launch_times), against 8 TB/s; the
-    whole step's figures and every launch kind's beside it.
+    whole step's figures and every launch kind's beside it;
+  * algorithmic: L-bar from the instrumented host emulation (`_lbar`).
+
+`--dump-outputs DIR` (rank 0): what a caller of the timed path holds after the last timed step, as
+float64 .npy files -- `verdicts.npy` (k, 2, 5): conj_id, action, table, tier, flags of both stages
+for a fixed seeded sample of k <= 2^18 packets, `verdicts_index.npy` (k,): their packet indices,
+and, with counters on, `counters.npy` (slots, 3): the per-rule counters accumulated over the timed
+steps. Inputs are seeded, so two builds run with the same arguments can be compared file for file
+(C5 excepted: its op batching follows the clock).
 """
 from __future__ import annotations
 
@@ -626,6 +641,42 @@ def _roofline(pmc, kern_ms, n, b_in, b_out, lbar, launches):
     return rl
 
 
+DUMP_SEED = 20240607
+DUMP_PACKETS = 1 << 18  # (k, 2, 5) float64 = 21 MB; with index and counters well under 64 MB
+DUMP_COUNTER_ROWS = 1 << 20  # (rows, 3) float64 = 25 MB at most
+
+
+def _sample_outputs(out, n, counters, k=DUMP_PACKETS):
+    """The arrays --dump-outputs writes, copied to the host right after the timed region: the verdicts
+    of a fixed seeded sample of k packets of the batch (all of it when n <= k), field by field as
+    float64, the sampled packet indices, and the per-rule counters (int64 tensor or None; a seeded
+    sample of its rows beyond DUMP_COUNTER_ROWS)."""
+    import numpy as np
+    import torch
+    from antrea_amd.gpc import VERDICT_DTYPE
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.arange(n, dtype=np.int64) if n <= k else np.sort(rng.integers(0, n, k))
+    v8 = out.view(torch.uint8).reshape(n, 2, 8)[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    v = np.ascontiguousarray(v8).view(VERDICT_DTYPE).reshape(-1, 2)
+    arrays = {"verdicts": np.stack([v[f].astype(np.float64) for f in VERDICT_DTYPE.names], axis=-1),
+              "verdicts_index": idx.astype(np.float64)}
+    if counters is not None:
+        c = counters.cpu().numpy().reshape(-1, 3)
+        if len(c) > DUMP_COUNTER_ROWS:
+            c = c[np.sort(rng.choice(len(c), DUMP_COUNTER_ROWS, replace=False))]
+        arrays["counters"] = c.view(np.uint64).astype(np.float64)
+    return arrays
+
+
+def _write_outputs(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 1000 * 1000
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    _log("wrote %s to %s" % (", ".join("%s.npy %s" % (k, a.shape) for k, a in arrays.items()), d))
+
+
 class _HipPath:
     """The product data path of one rank: gpc_classify* on this rank's GPU (the HIP kernels of
     libgpc.so), timed with HIP events on the launch stream, counters all-reduced over RCCL."""
@@ -814,11 +865,16 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3")
     ap.add_argument("--packets", type=int, default=1 << 26)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: oracle parity stamp, CPU baseline, rocprofv3 "
+                         "PMC child passes (counter roofline), L-bar of the host emulation, C5 oracle replay")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (seeded verdict sample, counters) as DIR/<name>.npy")
     ap.add_argument("--no-count", action="store_true", help="disable per-rule counters")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the timed batch")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC child passes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the oracle check of the timed batch")
+    ap.add_argument("--no-traffic", action="store_true", help="--full without the rocprofv3 PMC child passes")
     ap.add_argument("--keep-pmc", default="", help="directory that keeps the PMC passes' counter CSVs")
     ap.add_argument("--churn-rate", type=float, default=10000.0, help="C5: address ops per second")
     ap.add_argument("--max-batch", type=int, default=2000, help="C5: most address ops per gpc_commit")
@@ -847,6 +903,8 @@ def main(argv=None):
                     help="HIP ordinals of the --multidev slots (default 0..N-1; e.g. 0,0 = two slots on one GPU)")
     argv = sys.argv[1:] if argv is None else argv
     args = ap.parse_args(argv)
+    if not args.full:  # a plain run: the headline figure only
+        args.no_parity = args.no_cpu_baseline = args.no_traffic = True
     if args.multidev:
         return main_multidev(args)
     env_world = os.environ.get("WORLD_SIZE")
@@ -1022,6 +1080,9 @@ def main(argv=None):
             update["candidate_adds"] = len(cands)
         if world > 1:
             update["ranks"] = _churn_converge(churn_ops, wl, dev, world)
+    dump = None
+    if args.dump_outputs and rank == 0:  # before anything below classifies into `out` or counts again
+        dump = _sample_outputs(out, n, dp.counters() if count else None)
     gc.enable()  # (after the control thread stopped: the op log's first collection is long)
     kern_ms = sum(s.elapsed_time(e) for s, e in zip(starts, ends)) / args.steps
     launches = dp.launch_times()
@@ -1111,7 +1172,7 @@ def main(argv=None):
         if parity.get("mismatches"):
             print("PARITY FAILURE: %s" % json.dumps(parity), file=sys.stderr)
 
-    lbar = _lbar(wl, clf, family=args.family)
+    lbar = _lbar(wl, clf, family=args.family) if args.full else None
     b_in, b_out = (19 if getattr(wl, "services", None) else 17), 16  # +2 B len for C4
     if v6:
         b_in += 24  # 16-B instead of 4-B src / dst
@@ -1155,6 +1216,8 @@ def main(argv=None):
     if update is not None:
         res["update"] = update
         res["metric"] = "Mpps classified under AddPolicyRuleAddress/DeletePolicyRuleAddress churn @100k rules"
+    if dump is not None:
+        _write_outputs(args.dump_outputs, dump)
     print(json.dumps(res))
     sys.stdout.flush()
     if world > 1:
@@ -1241,6 +1304,12 @@ def main_multidev(args):
     all_slots(args.steps, evs)
     sync()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs:  # every slot's verdicts at the same seeded sample of its shard
+        dump = {}
+        for k, sl in enumerate(slots):
+            a = _sample_outputs(sl["out"], n, None, k=DUMP_PACKETS // n_slots)
+            dump["verdicts_slot%d" % k], dump["verdicts_index"] = a["verdicts"], a["verdicts_index"]
+        _write_outputs(args.dump_outputs, dump)
     slot_ms = [sum(a.elapsed_time(b) for a, b in zip(*evs[k])) / args.steps for k in range(n_slots)]
     total = n * args.steps * n_slots
     metrics = clf.network_policy_metrics() if count else {}

@@ -169,6 +169,20 @@ def verify(cases):
     return checked, {os.path.relpath(p, REF): hashlib.sha256("\n".join(l).encode()).hexdigest() for p, l in files.items()}
 
 
+def reachability_functions():
+    """Names of the functions of antreapolicy_test.go that call NewReachability (a list of names:
+    the fixture must have a case for each, helpers excepted)."""
+    has, cur = set(), None
+    with open(os.path.join(REF, "test/e2e/antreapolicy_test.go")) as f:
+        for line in f:
+            m = re.match(r"func (\w+)\(", line)
+            if m:
+                cur = m.group(1)
+            if cur and "NewReachability(" in line:
+                has.add(cur)
+    return sorted(has)
+
+
 def universe(c):
     u = c["universe"]
     if u == "xyz":
@@ -178,10 +192,12 @@ def universe(c):
     return em.Universe(u)
 
 
-def main():
-    checked, digests = verify(CASES)
+def fixture(checked, digests, functions):
+    """The fixture's content: what was read from the reference (step count, file digests, function
+    names) plus the transcription of `e2e_cases.CASES` with each step's full expected matrix."""
     out = {"about": "e2e reachability expectations of the reference (see make_e2e_reachability.py)",
-           "reference_files": digests, "steps_checked": checked, "cases": []}
+           "reference_files": digests, "steps_checked": checked,
+           "reachability_functions": functions, "cases": []}
     for c in CASES:
         u = universe(c)
         cc = dict(c)
@@ -192,6 +208,12 @@ def main():
             s2["expected"] = sorted([a, b, v] for (a, b), v in m.items())
             cc["steps"].append(s2)
         out["cases"].append(cc)
+    return out
+
+
+def main():
+    checked, digests = verify(CASES)
+    out = fixture(checked, digests, reachability_functions())
     with open(OUT, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
     print("wrote %s: %d cases, %d steps checked against the reference" % (OUT, len(CASES), checked))

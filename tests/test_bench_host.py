@@ -215,8 +215,8 @@ def test_bench_gpus2_launches_two_ranks():
     is the host emulation of the committed image, GPC_BENCH_HOST_EMU), all-reduce the per-rule
     counters, gather every rank's launch times, and rank 0 prints the one line with n_gpus == 2
     and its parity stamp against the oracle."""
-    rc, res, err = _run_bench(["--gpus", "2", "--config", "C1", "--packets", "4096", "--steps", "3", "--warmup", "1"],
-                              {"GPC_BENCH_HOST_EMU": "1"})
+    rc, res, err = _run_bench(["--gpus", "2", "--config", "C1", "--packets", "4096", "--steps", "3", "--warmup", "1",
+                               "--full"], {"GPC_BENCH_HOST_EMU": "1"})
     assert rc == 0, err[-3000:]
     assert res["n_gpus"] == 2 and res["config"]["parallelism"].endswith("x2, rules replicated")
     assert res["data"].startswith("host-emulation")
@@ -226,6 +226,39 @@ def test_bench_gpus2_launches_two_ranks():
     assert "rank 0's shard of 2" in res["parity"]["sample"]
     assert res["counters_allreduced"]["slots"] > 0 and res["counters_allreduced"]["packets"] > 0
     assert res["value"] > 0 and res["steps"] == 3
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) starts no oracle process, PMC pass or CPU baseline and still prints
+    the headline fields; --dump-outputs writes the last timed step's verdict sample and the
+    counters of the timed steps as float64 .npy, identical from run to run, and the dumped verdicts
+    are the host emulation's verdicts of the same seeded packets (host-emulation ranks)."""
+    from antrea_amd import gpc
+    from tests import emu
+    args = ["--gpus", "1", "--config", "C1", "--packets", "3000", "--steps", "2", "--warmup", "1"]
+    dumps = []
+    for d in ("a", "b"):
+        rc, res, err = _run_bench(args + ["--dump-outputs", str(tmp_path / d)], {"GPC_BENCH_HOST_EMU": "1"})
+        assert rc == 0, err[-3000:]
+        assert res["parity"] is None and res["cpu_baseline"] is None
+        assert res["roofline"]["pmc_by_kernel"] is None and res["roofline"]["algorithmic"]["lines_per_packet"] is None
+        assert res["steps"] == 2 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+        assert res["unit"] == "Mpps" and res["higher_is_better"] is True and res["dtype"] == "u32"
+        assert "rocprofv3" not in err and "parity check" not in err and "CPU baseline" not in err
+        dumps.append({f: np.load(tmp_path / d / (f + ".npy")) for f in ("verdicts", "verdicts_index", "counters")})
+    a, b = dumps
+    assert all(a[f].dtype == np.float64 and np.array_equal(a[f], b[f]) for f in a)
+    assert a["verdicts"].shape == (3000, 2, 5) and np.array_equal(a["verdicts_index"], np.arange(3000))
+    assert a["counters"].shape[1] == 3 and a["counters"][:, 0].sum() > 0
+    wl = workload.CONFIGS["C1"]()
+    clf = gpc.Classifier()
+    clf.initialize()
+    clf.batch_install_policy_rule_flows(wl.rules)
+    emu.commit_host(clf)
+    cols = workload.gen_packets_torch(wl, 3000, seed=workload.PKT_SEED, device="cpu")
+    want = emu.classify(clf, bench._host_sample(cols, slice(None)))
+    for j, f in enumerate(gpc.VERDICT_DTYPE.names):
+        assert np.array_equal(a["verdicts"][:, :, j], want[f].astype(np.float64)), f
 
 
 def test_bench_gpus_mismatch_with_launcher_fails():

@@ -119,7 +119,7 @@ def test_bench_multidev_two_slots():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--multidev", "2", "--multidev-devices", "0,0", "--config",
-           "C1", "--steps", "3", "--warmup", "1", "--packets", str(1 << 20), "--no-traffic", "--no-cpu-baseline"]
+           "C1", "--steps", "3", "--warmup", "1", "--packets", str(1 << 20), "--full", "--no-traffic", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -4,11 +4,11 @@
 cd "${GRAFT_REPO_ROOT:-.}" || exit 1
 O=gpurun_out/${1:?tag}; STEPS=${2:-3000}; shift 2
 mkdir -p "$O"
-timeout -k 10 300 python -u bench.py --config C3 --no-traffic --no-cpu-baseline > "$O/C3.json" 2> "$O/C3.err" || { tail -5 "$O/C3.err"; exit 1; }
+timeout -k 10 300 python -u bench.py --full --config C3 --no-traffic --no-cpu-baseline > "$O/C3.json" 2> "$O/C3.err" || { tail -5 "$O/C3.err"; exit 1; }
 k=0
 for set in "" "$@"; do
   k=$((k+1))
-  env $set timeout -k 10 600 python -u bench.py --config C5 --steps "$STEPS" --warmup 20 $C5ARGS > "$O/C5_$k.json" 2> "$O/C5_$k.err" \
+  env $set timeout -k 10 600 python -u bench.py --full --config C5 --steps "$STEPS" --warmup 20 $C5ARGS > "$O/C5_$k.json" 2> "$O/C5_$k.err" \
     || { tail -5 "$O/C5_$k.err"; exit 1; }
 done
 python3 - "$O" <<'PY'

@@ -11,5 +11,5 @@ if [ -n "$TESTS" ]; then
   tail -4 "$O/tests.log"; [ $rc -eq 0 ] || exit $rc
 fi
 echo "== bench $(date +%T)"
-timeout -k 10 600 python -u bench.py "$@" > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 600 python -u bench.py --full "$@" > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 cat "$O/bench.json"

@@ -6,8 +6,8 @@
 #           the later steps then load the box-built library)
 #   tests   pytest -m gpu (one process, per-test timeout)
 #   smoke   __graft_entry__.smoke()
-#   bench   python bench.py (default C3 line: PMC passes, parity stamp, CPU baseline)
-#   cfg:X   bench.py --config X (C1, C2, C2g, C4, C5) ; v6 = C3 in IPv6, v6m48 = the same over four /48s
+#   bench   python bench.py --full (default C3 line: PMC passes, parity stamp, CPU baseline)
+#   cfg:X   bench.py --full --config X (C1, C2, C2g, C4, C5) ; v6 = C3 in IPv6, v6m48 = the same over four /48s
 #   kt      rocprofv3 --kernel-trace --stats over a short bench run
 #   sq[:X]  rocprofv3 SQ counters (config X, default C3) ; tcc[:X] TCC hit / miss / EA read requests
 #   fetch / write  FETCH_SIZE / WRITE_SIZE of C3
@@ -45,7 +45,7 @@ for s in $STEPS; do
       tail -1 "$O/smoke.log" ;;
     bench)
       step bench
-      timeout -k 10 900 python -u bench.py --keep-pmc "$O/pmc_bench" > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+      timeout -k 10 900 python -u bench.py --full --keep-pmc "$O/pmc_bench" > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
       cat "$O/bench.json" ;;
     cfg:*)
       c=${s#cfg:}; step "bench $c"
@@ -56,7 +56,7 @@ for s in $STEPS; do
         C5) a="--config C5 --steps ${C5_STEPS:-3500} --warmup 20" ;;
         *) a="--config $c" ;;
       esac
-      timeout -k 10 900 python -u bench.py $a --keep-pmc "$O/pmc_$c" > "$O/bench_$c.json" 2> "$O/bench_$c.err" || { tail -20 "$O/bench_$c.err"; exit 1; }
+      timeout -k 10 900 python -u bench.py --full $a --keep-pmc "$O/pmc_$c" > "$O/bench_$c.json" 2> "$O/bench_$c.err" || { tail -20 "$O/bench_$c.err"; exit 1; }
       python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['ms_per_step'], d['kernel_ms_by_launch'], (d.get('parity') or {}).get('mismatches'))" "$O/bench_$c.json" $c ;;
     kt)
       step "rocprof kernel trace"

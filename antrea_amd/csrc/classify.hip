@@ -43,6 +43,7 @@ __device__ unsigned long long gpc_stamp_acc[32];  // [16 * (kStage == 2) + regio
 // kernels sort 256 packets across 4 waves, which needs the larger block.
 constexpr int kBlock = GPC_BLOCK;
 constexpr int kSortBlock = 256;
+constexpr uint32_t kParkCounted = 1u << 31;  // parked egress slot word: the stage is counted
 template <bool kSort>
 constexpr int block_threads() { return kSort ? kSortBlock : kBlock; }
 
@@ -119,7 +120,7 @@ __device__ __forceinline__ uint64_t sorted_index(const EpochArgs& ep, const gpc_
     if (kStage == 2) {  // packets the ingress launch settles without table work weigh nothing
       const uint32_t ea = (mid ? mid[i].y : out[i].y) & 0xffu;
       live = ea != RV_DROP && ea != RV_REJECT && ea != RV_ISO_DROP &&
-             !ingress_bypass(ep.hdr->isc, pk.dest ? pk.dest[i] : 0u, pk.ct_mark ? pk.ct_mark[i] : 0u);
+             !ingress_bypass(const_hdr(ep.hdr)->isc, pk.dest ? pk.dest[i] : 0u, pk.ct_mark ? pk.ct_mark[i] : 0u);
     }
     if (live) {
       const uint32_t src = pk.src[i], dst = pk.dst[i];
@@ -127,7 +128,7 @@ __device__ __forceinline__ uint64_t sorted_index(const EpochArgs& ep, const gpc_
       make_axes(p, src, dst, pk.sport[i], pk.dport[i], pk.proto[i], pk.out_port[i], pk.in_port ? pk.in_port[i] : 0u,
                 pk.svc_group ? pk.svc_group[i] : 0u, pk.tun_id ? pk.tun_id[i] : 0u, pk.ct_src ? pk.ct_src[i] : src,
                 pk.ct_dst ? pk.ct_dst[i] : dst, pk.ct_state ? pk.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK));
-      const Img im{ep.blob, ep.hdr, nullptr, nullptr};
+      const Img im{ep.blob, const_hdr(ep.hdr), nullptr, nullptr};
       est = scan_estimate(im, ep.sort_table[kStage - 1], p);
     }
   }
@@ -203,7 +204,7 @@ __device__ __forceinline__ uint32_t scan_key(const EpochArgs& ep, const gpc_pkt_
             has(AX_REG7) && in.svc_group ? in.svc_group[i] : 0u, has(AX_TUN) && in.tun_id ? in.tun_id[i] : 0u,
             has(AX_CTSRC) && in.ct_src ? in.ct_src[i] : src, has(AX_CTDST) && in.ct_dst ? in.ct_dst[i] : dst,
             has(AX_CTST) && in.ct_state ? in.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK));
-  const Img im{ep.blob, ep.hdr, nullptr, nullptr};
+  const Img im{ep.blob, const_hdr(ep.hdr), nullptr, nullptr};
   uint32_t e = 0, g = 0;
 #pragma unroll
   for (uint32_t t = 1; t <= 3; t++) {
@@ -333,15 +334,24 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
       reinterpret_cast<uint2*>(out)[2 * k + 1] = make_uint2(conj, packed);
     }
   };
+  // One round of column loads: every load is issued before anything waits for one of them. The
+  // columns whose default is another column's value (ct_src, ct_dst) are loaded through a selected
+  // pointer -- a value select would wait for src / dst at the wave-uniform branch, a second
+  // dependent round of streaming reads.
+  const uint32_t* const ct_src_col = pk.ct_src ? pk.ct_src : pk.src;
+  const uint32_t* const ct_dst_col = pk.ct_dst ? pk.ct_dst : pk.dst;
   uint32_t src = pk.src[i], dst = pk.dst[i];
-  const uint32_t ct_src = pk.ct_src ? pk.ct_src[i] : src;
-  const uint32_t ct_dst = pk.ct_dst ? pk.ct_dst[i] : dst;  // pre-NAT destination
+  const uint32_t ct_src = ct_src_col[i];
+  const uint32_t ct_dst = ct_dst_col[i];  // pre-NAT destination
   uint32_t dport = pk.dport[i];
   const uint32_t sport = pk.sport[i], proto = pk.proto[i];
   uint32_t out_port = pk.out_port[i];
   uint32_t svc_group = pk.svc_group ? pk.svc_group[i] : 0u;
   uint32_t dest = pk.dest ? pk.dest[i] : 0u;
-  const uint32_t ct_mark = pk.ct_mark ? pk.ct_mark[i] : 0u;
+  const uint32_t in_port = pk.in_port ? pk.in_port[i] : 0u;
+  const uint32_t tun_id = pk.tun_id ? pk.tun_id[i] : 0u;
+  const uint32_t ct_state = pk.ct_state ? pk.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK);
+  const uint32_t ct_mark = pk.ct_mark ? pk.ct_mark[i] : 0u;  // (last: its hairpin bit is tested first)
   // Service stage. kStage 0: one launch does it and both policy stages. kStage 1 / 2 (Service
   // batches split like the others): the egress launch runs it and parks the fields it rewrites
   // (destination, port, reg1 / reg7, destination mark) in park[i]; the ingress launch reads them back
@@ -385,12 +395,12 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
       out_port = pv.z;
       svc_group = pv.w;
     }
-    if (const uint32_t b = ingress_bypass(ep.hdr->isc, dest, ct_mark)) {  // IngressSecurityClassifier
+    if (const uint32_t b = ingress_bypass(const_hdr(ep.hdr)->isc, dest, ct_mark)) {  // IngressSecurityClassifier
       store2(i, 0u, pack_verdict(b & 0xffu, 0, 0, (b >> 8) ? 2u : 0u));
       return;
     }
   }
-  View im{{ep.blob, ep.hdr, nullptr, ep.pool}, {ep.pool, nullptr, nullptr, ep.pool}, 1u, ep.jhdr, 0u};
+  View im{{ep.blob, const_hdr(ep.hdr), nullptr, ep.pool}, {ep.pool, nullptr, nullptr, ep.pool}, 1u, ep.jhdr, 0u};
   if (kDelta != kModeBase) {
     const JournalHdr* jh = reinterpret_cast<const JournalHdr*>(ep.pool + ep.jhdr);
     im.ext = jh->ext_off;
@@ -400,8 +410,7 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
     }
   }
   Pkt p(pkt_lane, pkt_stride);
-  make_pkt(p, src, dst, sport, dport, proto, out_port, pk.in_port ? pk.in_port[i] : 0u, svc_group,
-           pk.tun_id ? pk.tun_id[i] : 0u, ct_src, ct_dst, pk.ct_state ? pk.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK),
+  make_pkt(p, src, dst, sport, dport, proto, out_port, in_port, svc_group, tun_id, ct_src, ct_dst, ct_state,
            view_bloom_axes(im));
   // The packet index is parked in the lane's LDS column for the walk and read back after it
   // ("memory" clobber: the reload, and that of the packet's ct_state in count_stage, cannot be
@@ -419,33 +428,53 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
     count_stage(s.v, s.slot, len, p.ax[AX_CTST], [&](uint32_t w, unsigned long long v) { atomicAdd(&copy[w], v); });
   };
   if constexpr (kStage == 0) {
-    // Both stages in one launch (Services): the egress half is counted and stored before the
-    // ingress walk, so nothing of it is held over that walk.
-    // (the ingress bypass is parked next to the index: nothing of the Service stage is held in a
-    // register over the egress walk)
-    pkt_lane[(kPktWords + 1) * pkt_stride] = ingress_bypass(ep.hdr->isc, dest, ct_mark);
-    const StageOut s1 = walk_stage<kDelta, false>(im, p, 1u, nullptr, nullptr);
-    const uint64_t i1 = late();
-    const uint32_t byp = pkt_lane[(kPktWords + 1) * pkt_stride];
-    count_one(s1, i1);
-    uint2* const o2 = reinterpret_cast<uint2*>(out);
-    if (gout) mid[i1] = make_uint2(s1.v.conj, s1.v.packed);  // grouped order (un-permuted afterwards)
-    else o2[2 * at(i1)] = make_uint2(s1.v.conj, s1.v.packed);
-    const uint32_t a1 = s1.v.packed & 0xffu;
-    uint32_t gc = 0u, gp = 0u;  // ingress NONE: dropped in egress
+    // Both stages in one launch. Nothing global happens between the two walks: the egress half
+    // {conj, packed, slot | counted << 31} is parked in the lane's LDS column next to the index and
+    // the ingress bypass (nothing of it, nor of the Service stage, is held in a register over a
+    // walk), and the tail issues the len load, both stages' counter adds and then one 16-B store of
+    // the pair. (Counted and stored between the walks, the egress half's memory-side atomics and
+    // two 4-B stores stood in front of the ingress walk's first wait.)
+    pkt_lane[(kPktWords + 1) * pkt_stride] = ingress_bypass(const_hdr(ep.hdr)->isc, dest, ct_mark);
+    uint32_t a1;
+    {
+      const StageOut s1 = walk_stage<kDelta, false>(im, p, 1u, nullptr, nullptr);
+      pkt_lane[(kPktWords + 2) * pkt_stride] = s1.v.conj;
+      pkt_lane[(kPktWords + 3) * pkt_stride] = s1.v.packed;
+      pkt_lane[(kPktWords + 4) * pkt_stride] = s1.slot | (s1.counted ? kParkCounted : 0u);  // slots are < 2^31
+      a1 = s1.v.packed & 0xffu;
+    }
+    lds_reload();
+    StageOut s2;  // ingress NONE: dropped in egress
+    s2.v.conj = s2.v.packed = s2.slot = 0u;
+    s2.counted = 0;
     if (a1 != RV_DROP && a1 != RV_REJECT && a1 != RV_ISO_DROP) {
-      if (byp) {  // IngressSecurityClassifier
-        gp = pack_verdict(byp & 0xffu, 0, 0, (byp >> 8) ? 2u : 0u);
+      if (const uint32_t byp = pkt_lane[(kPktWords + 1) * pkt_stride]) {  // IngressSecurityClassifier
+        s2.v.packed = pack_verdict(byp & 0xffu, 0, 0, (byp >> 8) ? 2u : 0u);
       } else {
-        const StageOut s2 = walk_stage<kDelta, false>(im, p, 4u, nullptr, nullptr);
-        count_one(s2, late());
-        gc = s2.v.conj;
-        gp = s2.v.packed;
+        s2 = walk_stage<kDelta, false>(im, p, 4u, nullptr, nullptr);
       }
     }
-    const uint64_t i2 = late();
-    if (gout) gout[i2] = make_uint2(gc, gp);
-    else o2[2 * at(i2) + 1] = make_uint2(gc, gp);
+    const uint64_t k = late();
+    StageOut s1;
+    s1.v.conj = pkt_lane[(kPktWords + 2) * pkt_stride];
+    s1.v.packed = pkt_lane[(kPktWords + 3) * pkt_stride];
+    const uint32_t es = pkt_lane[(kPktWords + 4) * pkt_stride];
+    s1.slot = es & ~kParkCounted;
+    s1.counted = (es & kParkCounted) != 0u;
+    if (count && (s1.counted || s2.counted)) {  // the Metric tables' counters of both stages
+      const uint32_t len = pk.len ? pk.len[k] : 0u;
+      const uint32_t cts = p.ax[AX_CTST];
+      unsigned long long* const copy = counters + size_t(blockIdx.x & ep.ctr_mask) * ep.ctr_stride;
+      auto add = [&](uint32_t w, unsigned long long v) { atomicAdd(&copy[w], v); };
+      if (s1.counted) count_stage(s1.v, s1.slot, len, cts, add);
+      if (s2.counted) count_stage(s2.v, s2.slot, len, cts, add);
+    }
+    if (gout) {  // grouped order (un-permuted afterwards)
+      mid[k] = make_uint2(s1.v.conj, s1.v.packed);
+      gout[k] = make_uint2(s2.v.conj, s2.v.packed);
+    } else {
+      out[at(k)] = make_uint4(s1.v.conj, s1.v.packed, s2.v.conj, s2.v.packed);
+    }
     return;
   }
   const StageOut s = walk_stage<kDelta, false>(im, p, kStage == 2 ? 4u : 1u, nullptr, nullptr);
@@ -464,7 +493,8 @@ __global__ __launch_bounds__(block_threads<kSort>()) __attribute__((amdgpu_waves
     unsigned long long* __restrict__ counters, int count, const uint32_t* __restrict__ orig, uint2* __restrict__ mid,
     uint32_t xcd_order, uint2* __restrict__ gout, uint4* __restrict__ park) {
   // per-lane packet axes / filter bits: a [word][lane] table in LDS (core.hpp Pkt)
-  __shared__ uint32_t pkt_lds[(kPktWords + 2) * block_threads<kSort>()];  // + the parked index and bypass
+  // + the parked index and bypass, and in the one-launch kernels the parked egress half (3 words)
+  __shared__ uint32_t pkt_lds[(kPktWords + (kStage == 0 ? 5 : 2)) * block_threads<kSort>()];
 #if defined(GPC_STAMPS)
   {
     uint32_t* st = gpc_stamp_lds();
@@ -653,7 +683,7 @@ __global__ void trace_kernel(EpochArgs ep, gpc_pkt_soa pk, uint4* __restrict__ o
     }
   }
   lb_out[0] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
-  View im{{ep.blob, ep.hdr, nullptr, ep.pool}, {ep.pool, nullptr, nullptr, ep.pool}, 1u, ep.jhdr, 0u};
+  View im{{ep.blob, const_hdr(ep.hdr), nullptr, ep.pool}, {ep.pool, nullptr, nullptr, ep.pool}, 1u, ep.jhdr, 0u};
   if (ep.pool) {
     const JournalHdr* jh = reinterpret_cast<const JournalHdr*>(ep.pool + ep.jhdr);
     if (jh->bdead_off) im.base.dead = ep.pool + jh->bdead_off;

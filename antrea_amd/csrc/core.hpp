@@ -14,6 +14,7 @@
 // driver index per clause 0/1: bucket -> ranks, so a packet only visits rules that can match.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "gpc.h"
@@ -229,6 +230,40 @@ struct ImageHdr {
                         // kBloomL4: some entry is not an exact-value entry (Pkt::l4m is needed)
   uint32_t live;        // bit t - 1: table t has rules (hard or soft); an empty table is a miss
 };
+// The image header as the evaluation reads it. A base image is written once, before its epoch is
+// published, and never while a launch of that epoch runs, so every header field -- the same address
+// for all lanes -- is read through the constant address space: scalar loads that stay scalar after
+// the kernel's stores, atomics and compiler barriers (an ordinary global pointer loses that at the
+// first of them, and the uniform load then queues with the lanes' gathers). Sub-dword fields come
+// out of the aligned word that holds them. Per-lane gathers (directory blocks, entries, records,
+// point hash, BitSlots) stay ordinary loads from the blob.
+typedef GPC_CONST_AS ImageHdr CImageHdr;
+typedef GPC_CONST_AS TableHdr CTableHdr;
+typedef GPC_CONST_AS SubIdx CSubIdx;
+typedef GPC_CONST_AS HardFast CHardFast;
+typedef GPC_CONST_AS BitTable CBitTable;
+GPC_HD const CImageHdr* const_hdr(const ImageHdr* h) { return (const CImageHdr*)h; }
+// Byte fields of the header structs: gfx950 has no sub-dword scalar load, so a uint8_t field read
+// directly becomes a vector load; the accessors read the aligned word that holds it (both structs
+// are word-aligned; little-endian on the device and on the emulation's host alike).
+static_assert(offsetof(SubIdx, axis) == 0 && offsetof(SubIdx, band) == 1 && offsetof(SubIdx, bits) == 2 &&
+                  offsetof(SubIdx, fmt) == 3 && alignof(SubIdx) == 4,
+              "SubIdx: axis | band << 8 | bits << 16 | fmt << 24 in word 0");
+static_assert(offsetof(TableHdr, cband) % 4 == 0 && offsetof(TableHdr, cx) == offsetof(TableHdr, cband) + 1,
+              "TableHdr: cband | cx << 8 in one word");
+GPC_HD uint32_t si_word(const CSubIdx& si) { return *(const cword*)&si; }
+#if defined(__HIP_DEVICE_COMPILE__)
+// (host code that the device pass of a HIP source parses hands over a SubIdx in ordinary memory)
+GPC_HD uint32_t si_word(const SubIdx& si) { return si.axis | uint32_t(si.band) << 8 | uint32_t(si.bits) << 16 | uint32_t(si.fmt) << 24; }
+#endif
+// S: SubIdx as the header holds it (CSubIdx), or in ordinary memory
+template <typename S> GPC_HD uint32_t si_axis(const S& si) { return si_word(si) & 0xffu; }
+template <typename S> GPC_HD uint32_t si_band(const S& si) { return (si_word(si) >> 8) & 0xffu; }
+template <typename S> GPC_HD uint32_t si_bits(const S& si) { return (si_word(si) >> 16) & 0xffu; }
+template <typename S> GPC_HD uint32_t si_fmt(const S& si) { return si_word(si) >> 24; }
+GPC_HD uint32_t th_cword(const CTableHdr& th) { return *(const cword*)&th.cband; }
+GPC_HD uint32_t th_cband(const CTableHdr& th) { return th_cword(th) & 0xffu; }
+GPC_HD uint32_t th_cx(const CTableHdr& th) { return (th_cword(th) >> 8) & 0xffu; }
 // IngressSecurityClassifier (pipeline.go:2144-2182), from the installed flows: bit d (gpc_dest d =
 // gateway 1, tunnel 2, uplink 3) -- packets to that destination skip to IngressMetric; kIscHairpin
 // -- ct_mark HairpinCTMark skips to ConntrackCommit. All at one priority, so a packet hitting two of
@@ -390,7 +425,8 @@ extern "C" void gpc_emu_touch(const void* p, unsigned bytes, int line);
 #endif
 
 // core.hpp SubIdx fmt 1: bucket b's entry range [lo, hi) from its directory block
-GPC_HD void dir_list(const uint32_t* blob, const SubIdx& si, uint32_t b, uint32_t* lo, uint32_t* hi) {
+template <typename S>
+GPC_HD void dir_list(const uint32_t* blob, const S& si, uint32_t b, uint32_t* lo, uint32_t* hi) {
   const uint32_t* d = blob + si.off + 4u * (b >> 5);
   GPC_TOUCH(d, 16);
 #if defined(__HIPCC__)
@@ -414,7 +450,7 @@ GPC_HD uint64_t combo_key64(uint32_t v) { return (uint64_t(0xC0B0u) << 32) | v; 
 // Combination id of host value v (0: in no set of the sub-index): both 16-B buckets loaded together.
 GPC_HD uint32_t combo_of(const uint32_t* blob, uint32_t off, uint32_t v) {
   const uint32_t* t = blob + off;
-  const uint32_t mask = (1u << t[0]) - 1u;
+  const uint32_t mask = (1u << *(const cword*)t) - 1u;  // (the table's size word: a wave-uniform address)
   const uint64_t k = combo_key64(v);
   const uint32_t* b1 = t + 4 + 4 * size_t(hash_b1(k, mask));
   const uint32_t* b2 = t + 4 + 4 * size_t(hash_b2(k, mask));
@@ -428,12 +464,14 @@ GPC_HD uint32_t combo_of(const uint32_t* blob, uint32_t off, uint32_t v) {
   return (q1.x == v ? q1.y : 0u) | (q1.z == v ? q1.w : 0u) | (q2.x == v ? q2.y : 0u) | (q2.z == v ? q2.w : 0u);
 }
 // Bucket key of a composite sub-index for the packet: its band key, or its combination id.
-GPC_HD uint32_t ckey_of(const uint32_t* blob, const SubIdx& si, uint32_t v) {
-  return si.band == kBandCombo ? combo_of(blob, si.pres, v) : v;
+template <typename S>
+GPC_HD uint32_t ckey_of(const uint32_t* blob, const S& si, uint32_t v) {
+  return si_band(si) == kBandCombo ? combo_of(blob, si.pres, v) : v;
 }
 // Entries listed under bucket b of a sub-index (either format; host statistics).
-GPC_HD uint32_t sub_bucket_len(const uint32_t* blob, const SubIdx& si, uint32_t b) {
-  if (!si.fmt) return blob[si.off + b + 1] - blob[si.off + b];
+template <typename S>
+GPC_HD uint32_t sub_bucket_len(const uint32_t* blob, const S& si, uint32_t b) {
+  if (!si_fmt(si)) return blob[si.off + b + 1] - blob[si.off + b];
   uint32_t lo, hi;
   dir_list(blob, si, b, &lo, &hi);
   return hi - lo == kDirCountMax ? blob[4 * lo + 2] : hi - lo;
@@ -858,7 +896,7 @@ GPC_HD void v6_words(const uint8_t* p, uint32_t* a) {
 
 struct Img {
   const uint32_t* blob;
-  const ImageHdr* hdr;
+  const CImageHdr* hdr;
   const uint32_t* dead;   // tombstones over this image's rule ids (delta epochs), or null: a page table
   const uint32_t* dpool;  // of journal-pool word offsets, one 256-word (8192-bit) bitmap page each
 };
@@ -1206,7 +1244,7 @@ GPC_HD bool rule_match(const Img& im, const W* rec, uint32_t w2, const uint32_t*
 
 // An inline hard pseudo-rule (TableHdr.hf) against the packet: descriptor kinds are uniform, so
 // the only per-lane work is the compares (and the point-hash probe of an FK_HASH clause).
-GPC_HD bool hard_fast_match(const Img& im, const HardFast& hf, const Pkt& p) {
+GPC_HD bool hard_fast_match(const Img& im, const CHardFast& hf, const Pkt& p) {
   const uint32_t ncl = hf.pv >> 24;
   bool ok = true;
 #pragma unroll
@@ -1250,16 +1288,16 @@ GPC_HD bool entry_pass(const Pkt& p, const Ent& e, uint32_t xv, uint32_t cp = 0u
 // Scan length of one table for the packet (the driver clause's candidate count, as eval_part picks
 // it): the kernel can group lanes of similar length into the same wavefront (classify.hip).
 GPC_HD uint32_t scan_estimate(const Img& im, uint32_t table, const Pkt& p) {
-  const TableHdr& th = im.hdr->t[table - 1];
+  const CTableHdr& th = im.hdr->t[table - 1];
   if (th.n_cidx) {  // the composite driver is always taken (eval_part)
-    const uint32_t xb = cx_bit(p.ax[th.cx]);
+    const uint32_t xb = cx_bit(p.ax[th_cx(th)]);
     if (!((im.blob[th.xmap_off + (xb >> 5)] >> (xb & 31u)) & 1u)) return 0;
-    uint32_t c = th.always_n[th.cband];
+    uint32_t c = th.always_n[th_cband(th)];
     for (uint32_t i = 0; i < th.n_cidx && i < uint32_t(kIdxPerClause); i++) {
-      const SubIdx& si = th.cidx[i];
-      const uint32_t key = ckey_of(im.blob, si, p.ax[si.axis]);
-      if (si.band == kBandCombo && key == 0u) continue;
-      const uint32_t bk = cbucket_of(si.band, si.bits, key, p.ax[th.cx]);
+      const CSubIdx& si = th.cidx[i];
+      const uint32_t key = ckey_of(im.blob, si, p.ax[si_axis(si)]);
+      if (si_band(si) == kBandCombo && key == 0u) continue;
+      const uint32_t bk = cbucket_of(si_band(si), si_bits(si), key, p.ax[th_cx(th)]);
       c += sub_bucket_len(im.blob, si, bk);
     }
     return c;
@@ -1270,8 +1308,8 @@ GPC_HD uint32_t scan_estimate(const Img& im, uint32_t table, const Pkt& p) {
 #pragma unroll
     for (int i = 0; i < kIdxPerClause; i++) {
       if (uint32_t(i) >= th.n_idx[k]) break;
-      const SubIdx& si = th.idx[k][i];
-      const uint32_t* o = im.blob + si.off + bucket_of(si.axis, si.band, si.bits, p.ax[si.axis]);
+      const CSubIdx& si = th.idx[k][i];
+      const uint32_t* o = im.blob + si.off + bucket_of(si_axis(si), si_band(si), si_bits(si), p.ax[si_axis(si)]);
       uint32_t ob, oe;
       load_pair(o, &ob, &oe);
       cnt[k] += oe - ob;
@@ -1354,7 +1392,7 @@ GPC_HD void scan_lists(const Img& im, const Pkt& p, const uint32_t* dl, const ui
 // only (unrolled), so it stays in VGPRs.
 GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
   GPC_MARK(ST_HARD);
-  const TableHdr& th = im.hdr->t[table - 1];
+  const CTableHdr& th = im.hdr->t[table - 1];
   TablePart res;
   res.h = res.s = res.win = 0;
   uint32_t htie = 0, noact = 0;
@@ -1367,7 +1405,7 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
     // and different verdicts; lower-priority ones after the first match do not count)
     bool stop = false;
     for (uint32_t h = 0; h < th.n_hfast; h++) {
-      const HardFast& hf = th.hf[h];
+      const CHardFast& hf = th.hf[h];
       if (rule_dead(im, hf.rid)) continue;
       const uint32_t prio = hf.pv & 0xffffu, verdict = (hf.pv >> 16) & 0xffu;
       const bool m = hard_fast_match(im, hf, p);
@@ -1409,7 +1447,7 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
   // res.h's kHFound bit (a separate flag was the base kernels' last spilled register)
   if (rH != th.end_off) res.h = hprio | (hverdict << 16) | kHFound | htie;
   if (th.bits_off && !im.dead) {  // bit-parallel table (tombstones: the scan below honours them)
-    const BitTable& bt = *reinterpret_cast<const BitTable*>(im.blob + th.bits_off);
+    const CBitTable& bt = *(const CBitTable*)(im.blob + th.bits_off);
     uint32_t s0 = bt.absent[0], s1 = bt.absent[1], s2 = bt.absent[2];
     const uint32_t np = bt.n_probe;
     constexpr uint32_t kBatch = 3;  // probes whose slot loads are in flight together (register budget)
@@ -1424,10 +1462,10 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
         key[j] = 0;
         c1[j] = c2[j] = BitSlot{1u, 0u};
         if (q < np) {
-          const BitProbe pr = bt.probe[q];
-          key[j] = p.ax[pr.ak & 15u] & pr.mask;
-          const uint32_t h = bit_hash(q, key[j]), m = (1u << pr.lg) - 1u;
-          const BitSlot* sl = reinterpret_cast<const BitSlot*>(im.blob + pr.off);
+          const uint32_t ak = bt.probe[q].ak, off = bt.probe[q].off, lg = bt.probe[q].lg;
+          key[j] = p.ax[ak & 15u] & bt.probe[q].mask;
+          const uint32_t h = bit_hash(q, key[j]), m = (1u << lg) - 1u;
+          const BitSlot* sl = reinterpret_cast<const BitSlot*>(im.blob + off);
           GPC_TOUCH(sl + (h & m), 8);
           GPC_TOUCH(sl + ((h >> 16) & m), 8);
           c1[j] = sl[h & m];
@@ -1453,9 +1491,11 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
     }
     if (done) {
       const uint32_t w = uint32_t(__builtin_ctz(done));
-      GPC_TOUCH(&bt.info[2 * w], 8);
+      // (a per-lane index: an ordinary load)
+      const uint32_t* info = im.blob + th.bits_off + uint32_t(offsetof(BitTable, info) / 4) + 2 * w;
+      GPC_TOUCH(info, 8);
       uint32_t roff, pe;
-      load_pair(&bt.info[2 * w], &roff, &pe);
+      load_pair(info, &roff, &pe);
       const uint32_t end = pe >> 16;  // rules w + 1 .. end - 1 share w's priority
       const uint32_t later = end >= 32u ? 0xffffffffu : (1u << end) - 1u;
       const bool tie = (done & later & ~((2u << w) - 1u)) != 0u;
@@ -1475,8 +1515,8 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
   uint32_t always_n = 0;  // entries of the driver's always list to scan
   uint32_t cp = 0;        // the packet's combination id (kBandCombo sub-index)
   if (nc) {
-    d = th.cband;
-    const uint32_t xv = p.ax[th.cx];
+    d = th_cband(th);
+    const uint32_t xv = p.ax[th_cx(th)];
     const uint32_t xb = cx_bit(xv);
     GPC_TOUCH(im.blob + th.xmap_off + (xb >> 5), 4);
     const bool xin = (im.blob[th.xmap_off + (xb >> 5)] >> (xb & 31u)) & 1u;  // else no soft rule can match
@@ -1489,12 +1529,12 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
     for (int i = 0; i < kIdxPerClause; i++) {
       key[i] = 0u;
       if (uint32_t(i) < nc) {
-        const SubIdx& si = th.cidx[i];
-        key[i] = si.band == kBandCombo ? combo_of(im.blob, si.pres, p.ax[si.axis]) : p.ax[si.axis];
-        if (si.band == kBandCombo) cp = key[i];
+        const CSubIdx& si = th.cidx[i];
+        key[i] = si_band(si) == kBandCombo ? combo_of(im.blob, si.pres, p.ax[si_axis(si)]) : p.ax[si_axis(si)];
+        if (si_band(si) == kBandCombo) cp = key[i];
       }
     }
-    if (th.cidx[0].fmt) {
+    if (si_fmt(th.cidx[0])) {
       // bucket directories: one 16-B block per sub-index (and a pointer entry where a bucket
       // overflowed), read in the value-map word's round (fmt 1) or, where the map filters most
       // packets, only for the packets in it (fmt 2). The branch is wave-uniform, so the fmt-1 loads
@@ -1502,19 +1542,19 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
       bool ovf = false;
 #pragma unroll
       for (int i = 0; i < kIdxPerClause; i++) lo0[i] = hi0[i] = lo1[i] = hi1[i] = 0;
-      if (th.cidx[0].fmt == 1) {
+      if (si_fmt(th.cidx[0]) == 1) {
 #pragma unroll
         for (int i = 0; i < kIdxPerClause; i++)
-          if ((uint32_t(i) < nc) && (th.cidx[i].band != kBandCombo || key[i] != 0u)) {
-            const SubIdx& si = th.cidx[i];
-            dir_list(im.blob, si, cbucket_of(si.band, si.bits, key[i], xv), &lo0[i], &hi0[i]);
+          if ((uint32_t(i) < nc) && (si_band(th.cidx[i]) != kBandCombo || key[i] != 0u)) {
+            const CSubIdx& si = th.cidx[i];
+            dir_list(im.blob, si, cbucket_of(si_band(si), si_bits(si), key[i], xv), &lo0[i], &hi0[i]);
           }
       } else {
 #pragma unroll
         for (int i = 0; i < kIdxPerClause; i++)
-          if ((uint32_t(i) < nc) & xin && (th.cidx[i].band != kBandCombo || key[i] != 0u)) {
-            const SubIdx& si = th.cidx[i];
-            dir_list(im.blob, si, cbucket_of(si.band, si.bits, key[i], xv), &lo0[i], &hi0[i]);
+          if ((uint32_t(i) < nc) & xin && (si_band(th.cidx[i]) != kBandCombo || key[i] != 0u)) {
+            const CSubIdx& si = th.cidx[i];
+            dir_list(im.blob, si, cbucket_of(si_band(si), si_bits(si), key[i], xv), &lo0[i], &hi0[i]);
           }
       }
 #pragma unroll
@@ -1544,8 +1584,8 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
     for (int i = 0; i < kIdxPerClause; i++) {
       bk[i] = pw[i] = 0;
       if (uint32_t(i) < nc) {
-        const SubIdx& si = th.cidx[i];
-        bk[i] = cbucket_of(si.band, si.bits, key[i], xv);
+        const CSubIdx& si = th.cidx[i];
+        bk[i] = cbucket_of(si_band(si), si_bits(si), key[i], xv);
         if (si.pres) {
           GPC_TOUCH(im.blob + si.pres + (bk[i] >> 5), 4);
           pw[i] = im.blob[si.pres + (bk[i] >> 5)];
@@ -1558,7 +1598,7 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
     for (int i = 0; i < kIdxPerClause; i++) {
       lo0[i] = hi0[i] = lo1[i] = hi1[i] = 0;
       if ((uint32_t(i) < nc) & xin & ((pw[i] >> (bk[i] & 31u)) & 1u)) {
-        const SubIdx& si = th.cidx[i];
+        const CSubIdx& si = th.cidx[i];
         const uint32_t* o = im.blob + si.off;
         GPC_TOUCH(o + bk[i], 8);
         uint32_t ob, oe;
@@ -1577,8 +1617,8 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
     for (int i = 0; i < kIdxPerClause; i++) {
       lo0[i] = hi0[i] = lo1[i] = hi1[i] = 0;
       if (uint32_t(i) < n0) {
-        const SubIdx& si = th.idx[0][i];
-        const uint32_t b = bucket_of(si.axis, si.band, si.bits, p.ax[si.axis]);
+        const CSubIdx& si = th.idx[0][i];
+        const uint32_t b = bucket_of(si_axis(si), si_band(si), si_bits(si), p.ax[si_axis(si)]);
         const uint32_t* o = im.blob + si.off;
         GPC_TOUCH(o + b, 8);
         uint32_t ob, oe;
@@ -1588,8 +1628,8 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
         cnt0 += hi0[i] - lo0[i];
       }
       if (uint32_t(i) < n1) {
-        const SubIdx& si = th.idx[1][i];
-        const uint32_t b = bucket_of(si.axis, si.band, si.bits, p.ax[si.axis]);
+        const CSubIdx& si = th.idx[1][i];
+        const uint32_t b = bucket_of(si_axis(si), si_band(si), si_bits(si), p.ax[si_axis(si)]);
         const uint32_t* o = im.blob + si.off;
         GPC_TOUCH(o + b, 8);
         uint32_t ob, oe;
@@ -1621,7 +1661,7 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
   }
   const uint32_t total = upto[kLists - 1];
   const bool one_idx = nc ? nc <= 1 : n0 <= 1 && n1 <= 1;  // table-uniform: every driver list set has <= 1 sub-index
-  const uint32_t xv = nc ? p.ax[th.cx] : 0u;  // exact-value entries exist only in composite lists
+  const uint32_t xv = nc ? p.ax[th_cx(th)] : 0u;  // exact-value entries exist only in composite lists
   uint32_t after = 0;       // rescan bound (exclusive); record offsets are > 0
   int have = 0;             // result found
   uint32_t level = 0xffffffffu;
@@ -1795,13 +1835,13 @@ GPC_HD TablePart eval_journal(const View& v, uint32_t table, const Pkt& p) {
   // other one holds the AppliedTo values, whose chains list every changed rule of a Pod), chosen
   // without reading any head; else the clause with the shorter chains (saturating chain lengths).
   uint32_t d;
-  const TableHdr& bt = v.base.hdr->t[table - 1];
+  const CTableHdr& bt = v.base.hdr->t[table - 1];
 #if defined(GPC_JOURNAL_COUNT_ALWAYS)  // experiments: the pre-composite choice
   if (false) {
 #else
   if (bt.n_cidx) {  // (every soft rule has clauses 0 and 1: one-clause rules compile to plain flows)
 #endif
-    d = bt.cband;
+    d = th_cband(bt);
   } else {
     uint32_t cnt[2] = {jt.always[0] >> 24, jt.always[1] >> 24};
 #pragma unroll
@@ -1823,7 +1863,7 @@ GPC_HD TablePart eval_journal(const View& v, uint32_t table, const Pkt& p) {
       const uint32_t axis = jt.kinds[d][i] & 15u, band = jt.kinds[d][i] >> 4;
       meta = jmeta(table, d, axis, band);
       key = jkey(axis, band, p.ax[axis]);
-      if (bt.n_cidx) key = jxkey(key, p.ax[bt.cx]);
+      if (bt.n_cidx) key = jxkey(key, p.ax[th_cx(bt)]);
       e = jhead(pool, jh, jbucket(meta, key, jh->lg));
     }
     const bool always = i == jt.n_kinds[d];
@@ -1929,7 +1969,7 @@ GPC_HD uint32_t ext_hash_x(uint32_t table, uint32_t axis, uint32_t v, uint32_t x
 // The probe hash of kind bit b (ExtHdr axes) for packet p.
 GPC_HD uint32_t ext_kind_hash(const View& v, uint32_t table, uint32_t b, const Pkt& p) {
   const uint32_t a = b & 15u;
-  return b < 16u ? ext_hash(table, a, p.ax[a]) : ext_hash_x(table, a, p.ax[a], p.ax[v.base.hdr->t[table - 1].cx]);
+  return b < 16u ? ext_hash(table, a, p.ax[a]) : ext_hash_x(table, a, p.ax[a], p.ax[th_cx(v.base.hdr->t[table - 1])]);
 }
 
 // The presence words of a table's extended axes (at most two; more: scanned unconditionally),
@@ -1984,7 +2024,7 @@ GPC_HD TablePart eval_ext(const View& v, uint32_t table, const Pkt& p, uint32_t 
   const ExtHdr* eh = reinterpret_cast<const ExtHdr*>(pool + v.ext);
   uint32_t axes = eh->axes[table - 1];
   uint32_t best = 0, best_prio = 0, best_conj = 0, at_best = 0;
-  const uint32_t xv = p.ax[v.base.hdr->t[table - 1].cx];  // (composite entries)
+  const uint32_t xv = p.ax[th_cx(v.base.hdr->t[table - 1])];  // (composite entries)
   for (uint32_t i = 0; axes; i++) {
     const uint32_t b = uint32_t(__builtin_ctz(axes)), a = b & 15u;
     axes &= axes - 1u;

@@ -114,6 +114,7 @@ struct DevEpoch {
   uint32_t jhdr = 0;                    // this epoch's JournalHdr in the pool (0: base only)
   int jmode = kModeBase;                // what the kernel reads of it (Journal::mode: point extensions only, or the journal)
   std::shared_ptr<DevImage> svc;        // Service image (d_hdr unused), shared until Services change
+  std::shared_ptr<DevImage> svc6;       // IPv6 Service image, under the same rules
   std::shared_ptr<DevImage> v6;         // IPv6 base image (ipv6_enabled), shared by its delta epochs
   std::shared_ptr<DevImage> v6_pool;    // journal pool of that base (append-only)
   uint32_t v6_jhdr = 0;                 // this epoch's IPv6 JournalHdr (0: base only)
@@ -213,6 +214,7 @@ struct gpc_ctx {
   FeatureNP np;
   FeatureService svc;
   std::vector<uint32_t> svc_blob;        // host copy of the Service image (empty: no Services)
+  std::vector<uint32_t> svc6_blob;       // host copy of the IPv6 Service image (empty: no IPv6 Services)
   uint64_t svc_gen = ~0ull;              // FeatureService generation the image was built from
   SlotMap slots;
   HostImage last;    // base image of the current epoch: shadow state for re-upload + debug export
@@ -926,13 +928,8 @@ int gpc_uninstall_pod(gpc_ctx* ctx, const uint8_t* ip, uint8_t family) {
   GPC_SVC_CALL(ctx->svc.uninstall_pod(ip, family));
 }
 int gpc_set_node_port_addresses(gpc_ctx* ctx, const uint8_t* ips, uint8_t family, size_t n) {
-  if ((!ips && n) || family != 4 || n > kSvcMaxNodePortAddrs - 1) return -GPC_EINVAL;
-  std::vector<uint32_t> v4(n);
-  for (size_t i = 0; i < n; i++) {
-    const uint8_t* b = ips + 16 * i;
-    v4[i] = (uint32_t(b[0]) << 24) | (uint32_t(b[1]) << 16) | (uint32_t(b[2]) << 8) | b[3];
-  }
-  GPC_SVC_CALL(ctx->svc.set_node_port_addresses(v4.data(), n));
+  if ((!ips && n) || (family != 4 && family != 6) || n > kSvcMaxNodePortAddrs - 1) return -GPC_EINVAL;
+  GPC_SVC_CALL(ctx->svc.set_node_port_addresses(ips, family, n));
 }
 
 int gpc_dump_groups(gpc_ctx* ctx, char* buf, size_t cap, size_t* needed) {
@@ -1108,6 +1105,7 @@ int gpc_replay(gpc_ctx* ctx) {
       }
     }
     if (!rc && !ctx->svc_blob.empty()) rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc);
+    if (!rc && !ctx->svc6_blob.empty()) rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6);
     if (!rc && (hip_ok(hipMalloc(&nc[k], cap * kCounterBytes * (copies + 1))) ||
                 hip_ok(hipMemset(nc[k], 0, cap * kCounterBytes * (copies + 1)))))
       rc = -GPC_EDEV;
@@ -1337,11 +1335,23 @@ int gpc_classify_host(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict
 }
 
 int gpc_classify6(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, int32_t count, void* stream) {
-  return gpc_classify6_on(ctx, 0, pk, n, out, count, stream);
+  return gpc_classify6_lb_on(ctx, 0, pk, n, out, nullptr, count, stream);
+}
+
+int gpc_classify6_lb(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out, int32_t count,
+                     void* stream) {
+  return gpc_classify6_lb_on(ctx, 0, pk, n, out, lb_out, count, stream);
 }
 
 int gpc_classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, int32_t count,
                      void* stream) {
+  return gpc_classify6_lb_on(ctx, slot, pk, n, out, nullptr, count, stream);
+}
+
+int gpc_classify6_lb_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
+                        gpc_lb_result6* lb_out, int32_t count, void* stream) {
+  static_assert(sizeof(gpc_lb_result6) == 32, "two 128-bit stores per packet (classify.hip v6_lb_kernel)");
+  if (reinterpret_cast<uintptr_t>(lb_out) % 16) return -GPC_EINVAL;
   if (!ctx || !pk || (!out && n) || n > GPC_MAX_BATCH || slot >= ctx->dev.size()) return -GPC_EINVAL;
   if (n && (!pk->src6 || !pk->dst6 || !pk->sport || !pk->dport || !pk->proto || !pk->out_port)) return -GPC_EINVAL;
   for (const void* c : {(const void*)pk->src6, (const void*)pk->dst6, (const void*)pk->ct_src6, (const void*)pk->ct_dst6})
@@ -1358,11 +1368,21 @@ int gpc_classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t 
   // the grouping scratch of the IPv4-shaped batch over those columns (address key: the top byte of
   // the source code, i.e. the batch's source prefixes in tree order)
   GroupArgs ga{nullptr, GPC_GROUP_KEY_ADDR, 0u, 8u, ctx->group_xcd, ctx->group_unpermute, 0u};
-  const size_t code_bytes = (size_t(v6_code_columns(*pk)) * n * 4 + 255) & ~size_t(255);
+  // an IPv6 Service image is bound: the Service stage runs first (classify.hip v6_lb_kernel) and its
+  // rewritten columns follow the code columns in the scratch; the code batch then has ct_dst (the
+  // pre-NAT destination), svc_group and dest columns whatever the caller gave
+  const uint32_t* const svc6 = D.cur.svc6 ? D.cur.svc6->d_blob : nullptr;
+  const size_t code_words = (size_t(v6_code_columns(*pk, svc6 != nullptr)) * n * 4 + 255) & ~size_t(255);
+  const size_t code_bytes = code_words + (svc6 ? (size_t(v6_lb_scratch_bytes(n)) + 255) & ~size_t(255) : 0);
   gpc_pkt_soa shape = *pk;  // which columns the code batch has (group_scratch_bytes reads presence only)
   shape.src = shape.dst = reinterpret_cast<const uint32_t*>(pk->src6);
   shape.ct_src = pk->ct_src6 ? shape.src : nullptr;
-  shape.ct_dst = pk->ct_dst6 ? shape.src : nullptr;
+  shape.ct_dst = pk->ct_dst6 || svc6 ? shape.src : nullptr;
+  if (svc6) {
+    shape.svc_group = shape.src;
+    shape.dest = pk->src6;
+  }
+  if (!svc6 && lb_out && n && hip_ok(hipMemsetAsync(lb_out, 0, n * sizeof(gpc_lb_result6), st))) return -GPC_EDEV;
   uint8_t* scratch = nullptr;
   if (n && ctx->group_v6 && group_batch(ctx, n, *D.cur.v6, D.cur.v6_jhdr != 0)) {
     if (const int e = group_scratch_for(ctx, D, st, code_bytes + group_scratch_bytes(shape, n, false), &scratch)) return e;
@@ -1371,7 +1391,8 @@ int gpc_classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t 
   if (n && !scratch)
     if (const int e = group_scratch(D, st, code_bytes, &scratch)) return e;
   int rc = launch_classify6(ep, *pk, n, out, D.d_counters, count, ga.scratch ? &ga : nullptr,
-                            reinterpret_cast<uint32_t*>(scratch), st, n ? next_marks(D) : nullptr);
+                            reinterpret_cast<uint32_t*>(scratch), st, n ? next_marks(D) : nullptr, svc6,
+                            svc6 && scratch ? scratch + code_words : nullptr, reinterpret_cast<uint4*>(lb_out));
   if (!rc && scratch) rc = group_scratch_used(D, st);
   if (rc || n == 0) return rc;
   pace.record();
@@ -1379,6 +1400,11 @@ int gpc_classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t 
 }
 
 int gpc_classify6_host(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, int32_t count) {
+  return gpc_classify6_host_lb(ctx, pk, n, out, nullptr, count);
+}
+
+int gpc_classify6_host_lb(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
+                          int32_t count) {
   if (!ctx || !pk || (!out && n)) return -GPC_EINVAL;
   if (hip_ok(hipSetDevice(ctx->dev[0].device))) return -GPC_EDEV;
   if (n == 0) return GPC_OK;
@@ -1412,11 +1438,15 @@ int gpc_classify6_host(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdic
   up(pk->len, 2, (const void**)&d.len);
   up(pk->ct_mark, 1, (const void**)&d.ct_mark);
   void* dout = nullptr;
+  void* dlb = nullptr;
   if (!rc && hip_ok(hipMalloc(&dout, n * 2 * sizeof(gpc_verdict)))) rc = -GPC_EDEV;
-  if (!rc) rc = gpc_classify6(ctx, &d, n, (gpc_verdict*)dout, count, nullptr);
+  if (!rc && lb_out && hip_ok(hipMalloc(&dlb, n * sizeof(gpc_lb_result6)))) rc = -GPC_EDEV;
+  if (!rc) rc = gpc_classify6_lb(ctx, &d, n, (gpc_verdict*)dout, (gpc_lb_result6*)dlb, count, nullptr);
   if (!rc && hip_ok(hipDeviceSynchronize())) rc = -GPC_EDEV;
   if (!rc && hip_ok(hipMemcpy(out, dout, n * 2 * sizeof(gpc_verdict), hipMemcpyDeviceToHost))) rc = -GPC_EDEV;
+  if (!rc && lb_out && hip_ok(hipMemcpy(lb_out, dlb, n * sizeof(gpc_lb_result6), hipMemcpyDeviceToHost))) rc = -GPC_EDEV;
   if (dout) (void)hipFree(dout);
+  if (dlb) (void)hipFree(dlb);
   for (void* p : allocs) (void)hipFree(p);
   return rc;
 }
@@ -1598,6 +1628,14 @@ int gpc_debug_service_image(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words
   return GPC_OK;
 }
 
+int gpc_debug_service_image6(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words) {
+  if (!ctx) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> g(ctx->ctl);
+  if (blob) *blob = ctx->svc6_blob.empty() ? nullptr : ctx->svc6_blob.data();
+  if (n_words) *n_words = ctx->svc6_blob.size();
+  return GPC_OK;
+}
+
 int gpc_set_launch_timing(gpc_ctx* ctx, uint32_t slots) {
   if (!ctx || slots > 4096) return -GPC_EINVAL;
   std::lock_guard<std::mutex> d(ctx->data);
@@ -1621,7 +1659,7 @@ int gpc_set_launch_timing(gpc_ctx* ctx, uint32_t slots) {
 int gpc_launch_times(gpc_ctx* ctx, gpc_launch_time* out, size_t cap, size_t* n) {
   if (!ctx || !n || (!out && cap)) return -GPC_EINVAL;
   static const char* const names[kLaunchKinds] = {"group_tiles", "classify_egress", "classify_ingress", "classify_both",
-                                                  "unpermute",   "v6_codes"};
+                                                  "unpermute",   "v6_codes",        "v6_lb"};
   double ms[kLaunchKinds] = {};
   uint32_t cnt[kLaunchKinds] = {};
   size_t dropped = 0;
@@ -1888,9 +1926,11 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
   const bool svc_changed = ctx->svc.generation() != ctx->svc_gen;
   if (svc_changed) {
     std::string err;
-    std::vector<uint32_t> sb;
+    std::vector<uint32_t> sb, sb6;
     if (!ctx->svc.empty() && (rc = ctx->svc.build_image(&sb, &err))) return rc;
+    if (!ctx->svc.empty() && ctx->cfg.ipv6_enabled && (rc = ctx->svc.build_image6(&sb6, &err))) return rc;
     ctx->svc_blob = std::move(sb);
+    ctx->svc6_blob = std::move(sb6);
     ctx->svc_gen = ctx->svc.generation();
   }
   ctx->slot_conj = ctx->slots.slot_conj();
@@ -2041,8 +2081,9 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
       ne[k].v6_lpm = ctx->last6.hdr.v6_lpm;
       ne[k].v6_gen = ctx->gen6;
     }
-    if (!svc_changed) ne[k].svc = D.cur.svc;
+    if (!svc_changed) ne[k].svc = D.cur.svc, ne[k].svc6 = D.cur.svc6;
     else if (!ctx->svc_blob.empty() && (rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc))) return fail(rc);
+    if (svc_changed && !ctx->svc6_blob.empty() && (rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6))) return fail(rc);
     ne[k].epoch = epoch;
     // counters: grow to the slot count, zero released slots (their Metric flows were deleted)
     nc[k] = D.d_counters;

@@ -98,6 +98,57 @@ __global__ __launch_bounds__(kCodeBlock) void v6_code_kernel(EpochArgs ep, V6Col
   codes[uint64_t(blockIdx.y) * n + i] = code;
 }
 
+// AntreaProxy stage of an IPv6 batch (core.hpp lb_stage6), in front of the code pass: the Service
+// lookup and the DNAT need the 128-bit destination, which the policy launches never see. One packet
+// per lane: dst6 (one 128-bit load), dport and proto in; src6 / sport only when the packet hits a
+// Service with Endpoints. Writes the columns the stage can rewrite -- the post-DNAT destination (16
+// network-order bytes, coded by v6_code_kernel in place of dst6), dport, out_port (reg1), svc_group
+// (reg7) and dest, whose bit kDestNoEndpoint tells the policy launch to reject the packet -- and the
+// optional gpc_lb_result6 at the caller index. A packet that hits no Service passes its inputs on.
+constexpr int kLbBlock = 256;
+struct V6LbArgs {
+  const uint32_t* svc;  // IPv6 Service image
+  const uint8_t *dst6, *src6;
+  const uint16_t *sport, *dport;
+  const uint8_t* proto;
+  const uint32_t *out_port, *svc_group;  // svc_group, dest: optional
+  const uint8_t* dest;
+  uint4* dst_out;
+  uint16_t* dport_out;
+  uint32_t *out_port_out, *svc_group_out;
+  uint8_t* dest_out;
+  uint4* lb_out;  // two per packet; may be null
+};
+__global__ __launch_bounds__(kLbBlock) void v6_lb_kernel(V6LbArgs a, uint64_t n) {
+  const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint4 v = reinterpret_cast<const uint4*>(a.dst6)[i];
+  uint32_t dst[4] = {__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w)};
+  uint32_t dport = a.dport[i];
+  const uint32_t proto = a.proto[i];
+  uint32_t out_port = a.out_port[i];
+  uint32_t svc_group = a.svc_group ? a.svc_group[i] : 0u;
+  uint32_t dest = a.dest ? a.dest[i] : 0u;
+  uint32_t lb[8];
+  const uint32_t f = lb_stage6(
+      a.svc,
+      [&]() {
+        const uint4 s = reinterpret_cast<const uint4*>(a.src6)[i];
+        return Svc6Src{__builtin_bswap32(s.x) ^ __builtin_bswap32(s.y) ^ __builtin_bswap32(s.z) ^ __builtin_bswap32(s.w),
+                       uint32_t(a.sport[i])};
+      },
+      dst, dport, proto, svc_group, out_port, dest, lb);
+  a.dst_out[i] = make_uint4(__builtin_bswap32(dst[0]), __builtin_bswap32(dst[1]), __builtin_bswap32(dst[2]), __builtin_bswap32(dst[3]));
+  a.dport_out[i] = uint16_t(dport);
+  a.out_port_out[i] = out_port;
+  a.svc_group_out[i] = svc_group;
+  a.dest_out[i] = uint8_t((dest & ~kDestNoEndpoint) | ((f & GPC_LB_NO_ENDPOINT) ? kDestNoEndpoint : 0u));
+  if (a.lb_out) {
+    a.lb_out[2 * i] = make_uint4(__builtin_bswap32(lb[0]), __builtin_bswap32(lb[1]), __builtin_bswap32(lb[2]), __builtin_bswap32(lb[3]));
+    a.lb_out[2 * i + 1] = make_uint4(lb[4], lb[5], lb[6], 0u);
+  }
+}
+
 // Lane regrouping for a policy stage launch: the candidate scan of a wavefront runs as long as its
 // longest lane (the wave-uniform trip count of eval_part), so when the host saw long driver lists
 // in the stage's main table (api.cpp lane_sort_tables) the block's packets are regrouped by their
@@ -307,7 +358,9 @@ __device__ __forceinline__ uint64_t logical_block(uint32_t mode) {
 // here as code columns (v6_code_kernel) against the IPv6 image.
 // Packet i of the batch through the Service stage (kSvc) and the policy stage(s) of the launch;
 // pkt_lane / pkt_stride: this lane's column of the block's [word][lane] packet table in LDS.
-template <int kDelta, bool kSvc, int kStage>
+// kRes: the Service stage already ran (v6_lb_kernel): the columns are the rewritten ones and bit
+// kDestNoEndpoint of `dest` marks a packet of a Service without Endpoints.
+template <int kDelta, bool kSvc, int kStage, bool kRes = false>
 __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t i, uint4* __restrict__ out,
                                              uint4* __restrict__ lb_out, unsigned long long* __restrict__ counters, int count,
                                              const uint32_t* __restrict__ orig, uint2* __restrict__ mid,
@@ -357,6 +410,24 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
   // (destination, port, reg1 / reg7, destination mark) in park[i]; the ingress launch reads them back
   // instead of repeating the lookup. NO_ENDPOINT: rejected in EndpointDNAT before the policy
   // stages, so the ingress launch sees a REJECT egress action and stores ingress NONE.
+  if constexpr (kRes) {
+    const bool noep = (dest & kDestNoEndpoint) != 0u;
+    dest &= ~kDestNoEndpoint;
+    if (kStage != 2 && noep) {  // as below: rejected before the policy stages, no counter touched
+      const uint32_t rj = pack_verdict(GPC_ACT_REJECT, GPC_VTABLE_ENDPOINT_DNAT, 0, 0);
+      if (kStage == 0 && gout) {
+        mid[i] = make_uint2(0u, rj);
+        gout[i] = make_uint2(0u, 0u);
+      } else if (kStage == 1 && mid) {
+        mid[i] = make_uint2(0u, rj);
+      } else if (kStage == 1) {
+        out[i] = make_uint4(0u, rj, 0u, 0u);
+      } else {
+        out[at(i)] = make_uint4(0u, rj, 0u, 0u);
+      }
+      return;
+    }
+  }
   if (kSvc && kStage == 2) {
     // (read after the egress-action check below)
   } else if (kSvc) {
@@ -527,6 +598,22 @@ __global__ __launch_bounds__(block_threads<kSort>()) __attribute__((amdgpu_waves
 #endif
 }
 
+// The policy launches of an IPv6 batch whose Service stage ran in v6_lb_kernel (classify_one kRes):
+// kernels of their own, so the Service-free ones above keep their code.
+template <int kDelta, int kStage, bool kSort = false>
+__global__ __launch_bounds__(block_threads<kSort>()) __attribute__((amdgpu_waves_per_eu(kDelta == kModeJournal ? GPC_DELTA_WAVES_PER_EU : kDelta == kModeExt ? GPC_EXT_WAVES_PER_EU : GPC_WAVES_PER_EU))) void classify_resolved_kernel(
+    EpochArgs ep, gpc_pkt_soa pk, uint64_t n, uint4* __restrict__ out, uint4* __restrict__ lb_out,
+    unsigned long long* __restrict__ counters, int count, const uint32_t* __restrict__ orig, uint2* __restrict__ mid,
+    uint32_t xcd_order, uint2* __restrict__ gout, uint4* __restrict__ park) {
+  __shared__ uint32_t pkt_lds[(kPktWords + (kStage == 0 ? 5 : 2)) * block_threads<kSort>()];
+  const uint64_t block_base = logical_block<kGroupTile / block_threads<kSort>()>(xcd_order) * block_threads<kSort>();
+  uint64_t i = block_base + threadIdx.x;
+  if constexpr (kSort) i = sorted_index<kStage>(ep, pk, n, out, mid, block_base, pkt_lds);
+  if (i >= n) return;
+  classify_one<kDelta, false, kStage, true>(ep, pk, i, out, lb_out, counters, count, orig, mid, gout, park,
+                                            pkt_lds + threadIdx.x, block_threads<kSort>(), uint32_t(block_base >> 32));
+}
+
 // Verdict pairs of a grouped batch in caller order: the egress half from mid (grouped order, every
 // mid_words words) and the ingress half from gout (grouped order, both written with coalesced
 // stores by the classification launches) joined and stored at the caller index; with lbg, the
@@ -608,7 +695,7 @@ static void launch_unpermute(const void* mid, uint32_t mid_words, const uint2* g
                      reinterpret_cast<const uint32_t*>(mid), mid_words, gout, orig, n, out, lbg, lb_out);
 }
 
-template <int kDelta, bool kSvc>
+template <int kDelta, bool kSvc, bool kRes = false>
 static void launch(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out, uint4* lb_out,
                    unsigned long long* counters, int count, const uint32_t* orig, uint2* mid, uint32_t xo, uint2* gout,
                    uint4* park, hipStream_t stream, LaunchMarks* marks) {
@@ -637,6 +724,30 @@ static void launch(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_v
   static const int fused_env = std::getenv("GPC_FUSED") ? std::atoi(std::getenv("GPC_FUSED")) : -1;
   // (journal epochs keep the split: their fused kernel would spill at 5 waves)
   const bool fused = fused_env == 1 || (fused_env < 0 && kDelta != kModeJournal && !ep.sort_table[0] && !ep.sort_table[1]);
+  if constexpr (kRes) {  // the same choice of launches over the resolved kernels
+    const uint64_t sb = (n + kSortBlock - 1) / kSortBlock;
+    if (fused) {
+      launch_mark(marks, kLaunchBoth, stream);
+      hipLaunchKernelGGL((classify_resolved_kernel<kDelta, 0>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
+                         lb_out, counters, count, orig, mid, xo, gout, nullptr);
+      return;
+    }
+    launch_mark(marks, kLaunchEgress, stream);
+    if (ep.sort_table[0])
+      hipLaunchKernelGGL((classify_resolved_kernel<kDelta, 1, true>), dim3(uint32_t(sb)), dim3(kSortBlock), 0, stream, ep, pk,
+                         n, o, lb_out, counters, count, orig, mid, xo, nullptr, nullptr);
+    else
+      hipLaunchKernelGGL((classify_resolved_kernel<kDelta, 1>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
+                         lb_out, counters, count, orig, mid, xo, nullptr, nullptr);
+    launch_mark(marks, kLaunchIngress, stream);
+    if (ep.sort_table[1])
+      hipLaunchKernelGGL((classify_resolved_kernel<kDelta, 2, true>), dim3(uint32_t(sb)), dim3(kSortBlock), 0, stream, ep, pk,
+                         n, o, lb_out, counters, count, orig, mid, xo, gout, nullptr);
+    else
+      hipLaunchKernelGGL((classify_resolved_kernel<kDelta, 2>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
+                         lb_out, counters, count, orig, mid, xo, gout, nullptr);
+    return;
+  }
   if (fused) {
     launch_mark(marks, kLaunchBoth, stream);
     hipLaunchKernelGGL((classify_kernel<kDelta, false, 0>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
@@ -804,13 +915,19 @@ static int launch_group(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, 
   return 0;
 }
 
-uint32_t v6_code_columns(const gpc_pkt_soa& pk) { return 2u + (pk.ct_src6 ? 1u : 0u) + (pk.ct_dst6 ? 1u : 0u); }
+uint32_t v6_code_columns(const gpc_pkt_soa& pk, bool svc) {
+  return 2u + (pk.ct_src6 ? 1u : 0u) + (pk.ct_dst6 || svc ? 1u : 0u);
+}
+
+uint64_t v6_lb_scratch_bytes(uint64_t n) {  // dst6 dport out_port svc_group dest, every region 256-B aligned
+  return (16 + 2 + 4 + 4 + 1) * n + 5 * 256;
+}
 
 int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out,
                      unsigned long long* counters, int count, const GroupArgs* group, uint32_t* codes, hipStream_t stream,
-                     LaunchMarks* marks) {
+                     LaunchMarks* marks, const uint32_t* svc6, uint8_t* lb_scratch, uint4* lb_out6) {
   if (n == 0) return 0;
-  if (n > kMaxPackets || !codes) return -GPC_EINVAL;
+  if (n > kMaxPackets || !codes || (svc6 && !lb_scratch)) return -GPC_EINVAL;
   V6Cols cols{{pk.src6, pk.dst6, nullptr, nullptr}};
   uint32_t nc = 2;
   gpc_pkt_soa p4 = pk;  // the batch over code columns: src, dst [, ct_src] [, ct_dst]
@@ -818,12 +935,45 @@ int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc
   p4.src = codes;
   p4.dst = codes + n;
   p4.ct_src = p4.ct_dst = nullptr;
+  const uint8_t* ct_dst6 = pk.ct_dst6;
+  if (svc6) {  // the Service stage first: the code pass and the policy launches read what it rewrote
+    uint8_t* q = lb_scratch;
+    auto take = [&](uint64_t bytes) {
+      uint8_t* r = q;
+      q += (bytes + 255) & ~uint64_t(255);
+      return r;
+    };
+    V6LbArgs a{};
+    a.svc = svc6;
+    a.dst6 = pk.dst6;
+    a.src6 = pk.src6;
+    a.sport = pk.sport;
+    a.dport = pk.dport;
+    a.proto = pk.proto;
+    a.out_port = pk.out_port;
+    a.svc_group = pk.svc_group;
+    a.dest = pk.dest;
+    a.dst_out = reinterpret_cast<uint4*>(take(16 * n));
+    a.out_port_out = reinterpret_cast<uint32_t*>(take(4 * n));
+    a.svc_group_out = reinterpret_cast<uint32_t*>(take(4 * n));
+    a.dport_out = reinterpret_cast<uint16_t*>(take(2 * n));
+    a.dest_out = take(n);
+    a.lb_out = lb_out6;
+    launch_mark(marks, kLaunchV6Lb, stream);
+    hipLaunchKernelGGL(v6_lb_kernel, dim3(uint32_t((n + kLbBlock - 1) / kLbBlock)), dim3(kLbBlock), 0, stream, a, n);
+    cols.c[1] = reinterpret_cast<const uint8_t*>(a.dst_out);
+    p4.dport = a.dport_out;
+    p4.out_port = a.out_port_out;
+    p4.svc_group = a.svc_group_out;
+    p4.dest = a.dest_out;
+    if (!ct_dst6) ct_dst6 = pk.dst6;  // ct_ipv6_dst: the destination before the DNAT
+  }
   if (pk.ct_src6) {
     cols.c[nc] = pk.ct_src6;
     p4.ct_src = codes + uint64_t(nc++) * n;
   }
-  if (pk.ct_dst6) {
-    cols.c[nc] = pk.ct_dst6;
+  if (ct_dst6) {
+    cols.c[nc] = ct_dst6;
     p4.ct_dst = codes + uint64_t(nc++) * n;
   }
   launch_mark(marks, kLaunchCodes, stream);
@@ -832,12 +982,12 @@ int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc
     hipLaunchKernelGGL(v6_code_kernel<true>, grid, dim3(kCodeBlock), 0, stream, ep, cols, n, codes);
   else
     hipLaunchKernelGGL(v6_code_kernel<false>, grid, dim3(kCodeBlock), 0, stream, ep, cols, n, codes);
-  return launch_classify(ep, p4, n, out, nullptr, counters, count, group, stream, marks);
+  return launch_classify(ep, p4, n, out, nullptr, counters, count, group, stream, marks, nullptr, svc6 != nullptr);
 }
 
 int launch_classify(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out, uint4* lb_out,
                     unsigned long long* counters, int count, const GroupArgs* group, hipStream_t stream,
-                    LaunchMarks* marks, uint4* park) {
+                    LaunchMarks* marks, uint4* park, bool resolved) {
   if (n == 0) return 0;
   if (n > kMaxPackets) return -GPC_EINVAL;
   gpc_pkt_soa g;
@@ -861,7 +1011,11 @@ int launch_classify(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_
   // results) in grouped order for the un-permute, like the two launches without Services
   if (svc && lb_out && gout && !lbg) return -GPC_EINVAL;  // the caller sized the scratch without lb
   uint4* const lbk = lbg ? lbg : lb_out;
-  if (mode == kModeJournal && svc) launch<kModeJournal, true>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
+  if (resolved && svc) return -GPC_EINVAL;
+  if (resolved && mode == kModeJournal) launch<kModeJournal, false, true>(e, *p, n, out, nullptr, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
+  else if (resolved && mode == kModeExt) launch<kModeExt, false, true>(e, *p, n, out, nullptr, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
+  else if (resolved) launch<kModeBase, false, true>(e, *p, n, out, nullptr, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
+  else if (mode == kModeJournal && svc) launch<kModeJournal, true>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
   else if (mode == kModeJournal) launch<kModeJournal, false>(e, *p, n, out, lb_out, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
   else if (mode == kModeExt && svc) launch<kModeExt, true>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
   else if (mode == kModeExt) launch<kModeExt, false>(e, *p, n, out, lb_out, counters, count, orig, mid, xo, gout, nullptr, stream, marks);

@@ -102,6 +102,27 @@ static std::string ipmatch_str(const IPMatch& m) {  // utils.go getFieldDataStri
   return s;
 }
 
+static std::string hex128(const uint8_t* b) {  // getFieldDataString ByteArrayField: "%x" with the leading zeros trimmed
+  static const char* d = "0123456789abcdef";
+  std::string s;
+  for (int i = 0; i < 16; i++) {
+    s += d[b[i] >> 4];
+    s += d[b[i] & 15];
+  }
+  const size_t nz = s.find_first_not_of('0');
+  return "0x" + (nz == std::string::npos ? std::string("0") : s.substr(nz));
+}
+
+static IPAddr ip6_of(uint64_t hi, uint64_t lo) {
+  IPAddr a;
+  a.fam = 6;
+  for (int i = 0; i < 8; i++) {
+    a.b[i] = uint8_t(hi >> (56 - 8 * i));
+    a.b[8 + i] = uint8_t(lo >> (56 - 8 * i));
+  }
+  return a;
+}
+
 static std::string proto_str(uint16_t eth, uint8_t proto) {  // utils.go:298-354
   if (eth == kEthIP) {
     switch (proto) {
@@ -156,6 +177,7 @@ std::string Match::str(uint16_t priority) const {  // getFlowModMatch, utils.go:
       std::snprintf(buf, sizeof buf, ",reg%d=0x%x/0x%x", i, reg_v[i], reg_m[i]);
     s += buf;
   }
+  if (has_xxreg3) s += ",xxreg3=" + hex128(xxreg3);  // after the 32-bit registers (utils.go:1011-1015)
   if (has_tun) s += ",tun_id=" + std::to_string(tun_id);
   if (has_in_port) s += ",in_port=" + std::to_string(in_port);
   if (nw_src.set) s += std::string(nw_src.addr.fam == 4 ? ",nw_src=" : ",ipv6_src=") + ipmatch_str(nw_src);
@@ -196,6 +218,13 @@ std::string Action::str() const {  // utils.go:600-760 (the subset NP flows use)
                     "move:NXM_NX_REG0[0..3]->NXM_NX_CT_MARK[0..3]))",
                     table_name(uint8_t(a)), b, c >> 24, (c >> 16) & 255u, (c >> 8) & 255u, c & 255u, unsigned(lv));
       return buf;
+    case ACT_CT_DNAT6:
+      std::snprintf(buf, sizeof buf,
+                    "ct(commit,table=%s,zone=%u,nat(dst=[%s]:%u),exec(set_field:0x10/0x10->ct_mark,"
+                    "move:NXM_NX_REG0[0..3]->NXM_NX_CT_MARK[0..3]))",
+                    table_name(uint8_t(a)), b, ip6_of(lv, lm).str().c_str(), c);
+      return buf;
+    case ACT_SET_XXREG3: return "set_field:" + hex128(ip6_of(lv, lm).b) + "->xxreg3";
     case ACT_CT_HAIRPIN:  // podHairpinSNATFlow, pipeline.go:3052-3064
       std::snprintf(buf, sizeof buf, "ct(commit,table=%s,zone=%u,exec(set_field:0x20/0x20->ct_mark,set_field:0x40/0x40->ct_mark))",
                     table_name(uint8_t(a)), b);

@@ -2249,6 +2249,112 @@ GPC_HD uint32_t lb_stage(const uint32_t* sv, uint32_t src, uint32_t& dst, uint32
   return flags;
 }
 
+// ------------------------------------------------------------------------- IPv6 Service image
+// The AntreaProxy stage of IPv6 batches (service.cpp build_image6), looked up on the 128-bit
+// destination before it is coded (classify.hip v6_lb_kernel). Same SvcHdr and presence map; addresses
+// are four host-order words, most significant first:
+//   hash: 2-choice cuckoo, buckets of two 32-B slots {address[4], tag, service index, 0, 0}
+//   (tag = 1 << 31 | proto << 16 | port; 0 = empty), two 128-bit loads per slot; a NodePort Service
+//   is keyed by address 0;
+//   service records as in the IPv4 image {first endpoint, n_ep | slot_log2 << 24, group id, flags};
+//   endpoint records {address[4], port | flags << 16, out_port (reg1), destination class, 0};
+//   NodePort addresses: np_off, n_np entries of four words.
+constexpr uint32_t kSvc6SlotWords = 8, kSvc6BucketWords = kSvcSlots * kSvc6SlotWords, kSvc6EpWords = 8;
+// High bit of the rewritten `dest` byte handed to the policy launch: the packet hit a Service
+// without Endpoints (rejected in EndpointDNAT before the policy stages).
+constexpr uint32_t kDestNoEndpoint = 0x80u;
+GPC_HD uint32_t svc6_tag(uint32_t proto, uint32_t port) { return (1u << 31) | ((proto & 0xffu) << 16) | (port & 0xffffu); }
+// 64-bit digest of the key for the presence map and the bucket choice (never 0); the slot compare is
+// on the whole key.
+GPC_HD uint64_t svc6_hash_key(uint32_t proto, const uint32_t* a, uint32_t port) {
+  const uint64_t hi = (uint64_t(a[0]) << 32) | a[1], lo = (uint64_t(a[2]) << 32) | a[3];
+  return mix64(hi ^ mix64(lo ^ (uint64_t(svc6_tag(proto, port)) << 32))) | (1ull << 63);
+}
+struct Svc6Src {
+  uint32_t x, y;  // fold6(source address), sport
+};
+GPC_HD uint32_t fold6(const uint32_t* a) { return a[0] ^ a[1] ^ a[2] ^ a[3]; }
+// Index into the service records, or 0xffffffff.
+GPC_HD uint32_t svc6_lookup(const uint32_t* sv, uint32_t proto, const uint32_t* a, uint32_t port) {
+  const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+  const uint64_t key = svc6_hash_key(proto, a, port);
+  const uint32_t mb = svc_map_bit(key, h->map_log2);
+  GPC_TOUCH(sv + h->map_off + (mb >> 5), 4);
+  if (!((sv[h->map_off + (mb >> 5)] >> (mb & 31u)) & 1u)) return 0xffffffffu;
+  const uint32_t mask = (1u << h->hash_log2) - 1u;
+  const uint32_t bs[2] = {hash_b1(key, mask), hash_b2(key, mask)};
+  const uint32_t tag = svc6_tag(proto, port);
+  uint32_t r = 0xffffffffu;
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    const uint32_t* b = sv + h->hash_off + size_t(bs[c]) * kSvc6BucketWords;
+    GPC_TOUCH(b, 4 * kSvc6BucketWords);
+#pragma unroll
+    for (uint32_t i = 0; i < kSvcSlots; i++) {
+#if defined(__HIPCC__)
+      const uint4 k = reinterpret_cast<const uint4*>(b)[2 * i];
+      const uint4 v = reinterpret_cast<const uint4*>(b)[2 * i + 1];
+      const uint32_t w0 = k.x, w1 = k.y, w2 = k.z, w3 = k.w, t = v.x, si = v.y;
+#else
+      const uint32_t* s = b + kSvc6SlotWords * i;
+      const uint32_t w0 = s[0], w1 = s[1], w2 = s[2], w3 = s[3], t = s[4], si = s[5];
+#endif
+      r = (t == tag && w0 == a[0] && w1 == a[1] && w2 == a[2] && w3 == a[3]) ? si : r;
+    }
+  }
+  return r;
+}
+
+// The Service stage of one IPv6 packet: lb_stage over 128-bit addresses (dst: four host-order
+// words, rewritten by the DNAT). `src()` returns {fold6(source address), sport} and is called only
+// when the packet hits a Service with Endpoints. o[0..7] = gpc_lb_result6 words with o[0..3] the
+// Endpoint address as host-order words (the caller stores them in network order). The bucket:
+// lb_hash over the folded addresses -- the IPv4 bucket under a /96 embedding of both addresses.
+template <class SrcFn>
+GPC_HD uint32_t lb_stage6(const uint32_t* sv, SrcFn src, uint32_t* dst, uint32_t& dport, uint32_t proto, uint32_t& svc_group,
+                          uint32_t& out_port, uint32_t& dest, uint32_t* o) {
+  for (int k = 0; k < 8; k++) o[k] = 0;
+  if (proto != 6 && proto != 17 && proto != 132) return 0;
+  const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+  uint32_t si = svc6_lookup(sv, proto, dst, dport);
+  if (si == 0xffffffffu && h->n_np) {  // NodePortMark, then the NodePort ServiceLB flows
+    bool np = false;
+    for (uint32_t i = 0; i < h->n_np; i++) {
+      const uint32_t* a = sv + h->np_off + 4 * i;
+      np |= a[0] == dst[0] && a[1] == dst[1] && a[2] == dst[2] && a[3] == dst[3];
+    }
+    const uint32_t zero[4] = {0u, 0u, 0u, 0u};
+    if (np) si = svc6_lookup(sv, proto, zero, dport);
+  }
+  if (si == 0xffffffffu) return 0;
+  const uint32_t* s = sv + h->svc_off + 4 * si;
+  GPC_TOUCH(s, 16);
+  const uint32_t n = s[1] & 0xffffffu, lg = s[1] >> 24;
+  uint32_t flags = GPC_LB_HIT;
+  o[5] = s[2];
+  if (s[3] & kSvcLoadReg7) svc_group = s[2];
+  if (n == 0) {
+    flags |= GPC_LB_NO_ENDPOINT;
+    o[4] = flags << 16;
+    return flags;
+  }
+  const Svc6Src sp = src();
+  const uint32_t slot = lb_hash(sp.x, fold6(dst), sp.y, dport, proto) & ((1u << lg) - 1u);
+  const uint32_t* e = sv + h->ep_off + kSvc6EpWords * (s[0] + slot % n);
+  GPC_TOUCH(e, 4 * kSvc6EpWords);
+  flags |= e[4] >> 16;
+  o[0] = e[0], o[1] = e[1], o[2] = e[2], o[3] = e[3];
+  o[4] = (e[4] & 0xffffu) | (flags << 16);
+  o[6] = e[5];
+  if (flags & GPC_LB_DNAT) {
+    dst[0] = e[0], dst[1] = e[1], dst[2] = e[2], dst[3] = e[3];
+    dport = e[4] & 0xffffu;
+  }
+  out_port = e[5];
+  dest = e[6];
+  return flags;
+}
+
 // Verdict word layout (gpc_verdict): conj_id | action | table | tier | flags.
 struct VerdictOut {
   uint32_t conj;

@@ -53,7 +53,7 @@ struct LaunchMarks {
   int n;
 };
 enum LaunchKind : uint8_t {
-  kLaunchGroup, kLaunchEgress, kLaunchIngress, kLaunchBoth, kLaunchUnpermute, kLaunchCodes, kLaunchKinds, kLaunchEnd
+  kLaunchGroup, kLaunchEgress, kLaunchIngress, kLaunchBoth, kLaunchUnpermute, kLaunchCodes, kLaunchV6Lb, kLaunchKinds, kLaunchEnd
 };
 inline void launch_mark(LaunchMarks* m, uint8_t kind, hipStream_t s) {
   if (!m || m->n >= LaunchMarks::kMax) return;
@@ -63,13 +63,20 @@ inline void launch_mark(LaunchMarks* m, uint8_t kind, hipStream_t s) {
 // rewrites, handed from the egress launch to the ingress launch; null: one launch does both stages.
 int launch_classify(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out, uint4* lb_out,
                     unsigned long long* counters, int count, const GroupArgs* group, hipStream_t stream,
-                    LaunchMarks* marks = nullptr, uint4* park = nullptr);
+                    LaunchMarks* marks = nullptr, uint4* park = nullptr, bool resolved = false);
 // IPv6 batch (pk.src6 / dst6 [/ ct_src6 / ct_dst6]) against the IPv6 image `ep` (base or delta
 // epoch): v6_code_kernel maps the addresses to codes in `codes` (v6_code_columns(pk) * n words of
 // device memory, live until the launches have run), then launch_classify runs over the code columns
 // (`group`: sized by group_scratch_bytes of that IPv4-shaped batch).
-uint32_t v6_code_columns(const gpc_pkt_soa& pk);
+// svc6: the IPv6 Service image bound to the epoch (null: none, the launches above and nothing else).
+// With it v6_lb_kernel runs first (core.hpp lb_stage6) and writes the columns the Service stage
+// rewrites into lb_scratch (v6_lb_scratch_bytes(n) bytes) and the optional LB results (two uint4 per
+// packet, gpc_lb_result6) to lb_out6; the code pass then codes {src6, post-DNAT dst6, ct_src6?,
+// ct_dst6 or the original dst6}, and the policy launches run as `resolved` over those columns.
+uint32_t v6_code_columns(const gpc_pkt_soa& pk, bool svc = false);
+uint64_t v6_lb_scratch_bytes(uint64_t n);
 int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out,
                      unsigned long long* counters, int count, const GroupArgs* group, uint32_t* codes, hipStream_t stream,
-                     LaunchMarks* marks = nullptr);
+                     LaunchMarks* marks = nullptr, const uint32_t* svc6 = nullptr, uint8_t* lb_scratch = nullptr,
+                     uint4* lb_out6 = nullptr);
 }

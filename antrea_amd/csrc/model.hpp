@@ -93,6 +93,8 @@ struct Match {
   uint8_t nw_proto = 0;
   uint16_t reg_present = 0;
   uint32_t reg_v[16] = {0}, reg_m[16] = {0};
+  bool has_xxreg3 = false;  // xxreg3 (EndpointIP6Field): the 128-bit register an IPv6 Endpoint is loaded into
+  uint8_t xxreg3[16] = {0};
   bool has_tun = false;
   uint64_t tun_id = 0;
   bool has_in_port = false;
@@ -117,14 +119,16 @@ enum ActKind : uint8_t {
   ACT_CT_HAIRPIN,  // ct(commit,table=a,zone=b,exec(ConnSNATCTMark, HairpinCTMark))
   ACT_RESUBMIT,    // resubmit:a (group buckets)
   ACT_METER,       // meter:a
-  ACT_CONTROLLER   // controller(id=32776,reason=no_match,userdata=<a bytes of b, low first>,max_len=65535)
+  ACT_CONTROLLER,  // controller(id=32776,reason=no_match,userdata=<a bytes of b, low first>,max_len=65535)
+  ACT_SET_XXREG3,  // set_field:0x<lv lm>->xxreg3 (IPv6 group buckets)
+  ACT_CT_DNAT6     // ACT_CT_DNAT with nat(dst=[lv lm]:c)
 };
 
 struct Action {
   ActKind kind;
   uint32_t a = 0, b = 0, c = 0;  // CONJ: id, clause, n ; SET_REG: reg, value, mask ; CT: table, zone ; GOTO: table ; GROUP: id
   bool has_mask = false;
-  uint64_t lv = 0, lm = 0;       // CT: ct_label value/mask
+  uint64_t lv = 0, lm = 0;       // CT: ct_label value/mask ; SET_XXREG3 / CT_DNAT6: the address, high / low half
   std::string str() const;
 };
 

@@ -1,6 +1,7 @@
 // AntreaProxy flows / groups (service.hpp). Flow text is golden-exact against
 // pkg/agent/openflow/client_test.go:1024-1330 (Test_client_InstallServiceGroup,
-// Test_client_InstallEndpointFlows, Test_client_InstallServiceFlows).
+// Test_client_InstallEndpointFlows, Test_client_InstallServiceFlows), for both families: a family-6
+// Endpoint is loaded into / matched in xxreg3, its flows are tcp6 / udp6 / sctp6 with zone 65510.
 #include "service.hpp"
 
 #include <cstdio>
@@ -23,6 +24,8 @@ constexpr uint32_t kToExternal = 1u << 21;         // reg4[21]  ToExternalAddres
 constexpr uint32_t kVirtualNodePortDNAT = 0xa9fe00fcu;  // config.VirtualNodePortDNATIPv4 169.254.0.252
 constexpr uint32_t kRemoteEndpoint = 1u << 26;     // reg4[26]  RemoteEndpointRegMark
 constexpr uint32_t kEpUnionMask = 0x7ffffu;        // reg4[0..18] EpUnionField
+// config.VirtualNodePortDNATIPv6 fc01::aabb:ccdd:eefe (node_config.go:84)
+constexpr uint8_t kVirtualNodePortDNAT6[16] = {0xfc, 0x01, 0, 0, 0, 0, 0, 0, 0, 0, 0xaa, 0xbb, 0xcc, 0xdd, 0xee, 0xfe};
 
 uint8_t ip_proto(uint8_t p) {  // gpc_protocol -> IP protocol number
   switch (p) {
@@ -67,6 +70,17 @@ void match_reg(Match& m, int r, uint32_t v, uint32_t mask) {  // several marks o
   }
 }
 
+uint64_t half(const IPAddr& a, int h) {  // big-endian 64-bit half of an IPv6 address
+  uint64_t v = 0;
+  for (int i = 0; i < 8; i++) v = (v << 8) | a.b[8 * h + i];
+  return v;
+}
+
+void words_of(const uint8_t* b, uint32_t* w) {  // four big-endian 32-bit words, most significant first
+  for (int k = 0; k < 4; k++)
+    w[k] = (uint32_t(b[4 * k]) << 24) | (uint32_t(b[4 * k + 1]) << 16) | (uint32_t(b[4 * k + 2]) << 8) | b[4 * k + 3];
+}
+
 void set_proto(Match& m, uint8_t proto, uint8_t family) {
   m.has_dl = true;
   m.dl_type = family == 6 ? kEthIPv6 : kEthIP;
@@ -97,12 +111,19 @@ int FeatureService::install_service_group(uint32_t gid, bool affinity, const gpc
   }
   for (size_t i = 0; i < n; i++) {
     const gpc_endpoint& e = eps[i];
-    if (e.family != 4 && e.family != 6) return -GPC_EINVAL;
-    if (e.family == 6) return -GPC_EINVAL;  // IPv6 Endpoints: xxreg3 loads are not modelled
+    if (!family_ok(e.family)) return -GPC_EINVAL;
     Bucket b;
     b.id = uint32_t(i);
     if (!e.is_local && e.has_node_name && !e.is_node_ip) b.acts.push_back(set_reg(4, kRemoteEndpoint, kRemoteEndpoint));
-    b.acts.push_back(set_reg(3, to_ip(e.ip, 4).v4()));
+    if (e.family == 6) {  // EndpointIP6Field (pipeline.go:2582-2584)
+      const IPAddr a = to_ip(e.ip, 6);
+      Action x{ACT_SET_XXREG3};
+      x.lv = half(a, 0);
+      x.lm = half(a, 1);
+      b.acts.push_back(x);
+    } else {
+      b.acts.push_back(set_reg(3, to_ip(e.ip, 4).v4()));
+    }
     b.acts.push_back(set_reg(4, e.port, 0xffff));
     Action r{ACT_RESUBMIT};
     r.a = resubmit;
@@ -129,25 +150,35 @@ static std::string endpoint_key(const gpc_endpoint& e, uint8_t proto) {  // gene
 // InstallEndpointFlows (client.go:750-770): endpointDNATFlow (pipeline.go:2502-2528) per Endpoint,
 // plus podHairpinSNATFlow (pipeline.go:3052-3064) for local Endpoints.
 int FeatureService::install_endpoint_flows(uint8_t proto, uint8_t family, const gpc_endpoint* eps, size_t n) {
-  if (!ip_proto(proto) || family != 4) return -GPC_EINVAL;
+  if (!ip_proto(proto) || !family_ok(family)) return -GPC_EINVAL;
   std::map<std::string, std::vector<Flow>> add;
   for (size_t i = 0; i < n; i++) {
     const gpc_endpoint& e = eps[i];
-    if (e.family != 4) return -GPC_EINVAL;
-    const uint32_t ip = to_ip(e.ip, 4).v4();
+    if (e.family != family) return -GPC_EINVAL;
+    const IPAddr addr = to_ip(e.ip, family);
+    const uint32_t ip = addr.v4();
     std::vector<Flow> fl;
     Flow f;
     f.table = TB_ENDPOINT_DNAT;
     f.priority = kPriorityNormal;
     f.cookie = cookie();
-    set_proto(f.m, ip_proto(proto), 4);
-    f.m.set_reg(3, ip);
+    set_proto(f.m, ip_proto(proto), family);
     f.m.set_reg(4, kEpSelected | e.port, kEpUnionMask);
-    Action ct{ACT_CT_DNAT};
+    Action ct{family == 6 ? ACT_CT_DNAT6 : ACT_CT_DNAT};
     ct.a = dnat_next_table();
-    ct.b = kCtZone;
-    ct.c = ip;
-    ct.lv = e.port;
+    if (family == 6) {
+      f.m.has_xxreg3 = true;
+      std::memcpy(f.m.xxreg3, addr.b, 16);
+      ct.b = kCtZoneV6;
+      ct.c = e.port;
+      ct.lv = half(addr, 0);
+      ct.lm = half(addr, 1);
+    } else {
+      f.m.set_reg(3, ip);
+      ct.b = kCtZone;
+      ct.c = ip;
+      ct.lv = e.port;
+    }
     f.acts = {ct};
     fl.push_back(f);
     if (e.is_local) {
@@ -158,12 +189,12 @@ int FeatureService::install_endpoint_flows(uint8_t proto, uint8_t family, const 
       h.m.has_ct_state = true;
       h.m.ct_data = 0x21;  // +new+trk
       h.m.ct_mask = 0x21;
-      set_proto(h.m, 0, 4);
+      set_proto(h.m, 0, family);
       h.m.nw_src.set = h.m.nw_dst.set = true;
-      h.m.nw_src.addr = h.m.nw_dst.addr = to_ip(e.ip, 4);
+      h.m.nw_src.addr = h.m.nw_dst.addr = addr;
       Action hp{ACT_CT_HAIRPIN};
       hp.a = TB_SNAT;
-      hp.b = kCtZone;
+      hp.b = family == 6 ? kCtZoneV6 : kCtZone;
       h.acts = {hp};
       fl.push_back(h);
     }
@@ -175,7 +206,7 @@ int FeatureService::install_endpoint_flows(uint8_t proto, uint8_t family, const 
 }
 
 int FeatureService::uninstall_endpoint_flows(uint8_t proto, uint8_t family, const gpc_endpoint* eps, size_t n) {
-  if (!ip_proto(proto) || family != 4) return -GPC_EINVAL;
+  if (!ip_proto(proto) || !family_ok(family)) return -GPC_EINVAL;
   for (size_t i = 0; i < n; i++) cached_.erase(endpoint_key(eps[i], proto));
   generation_++;
   return GPC_OK;
@@ -189,16 +220,16 @@ static std::string service_key(const IPAddr& ip, uint16_t port, uint8_t proto) {
 
 // InstallServiceFlows (client.go:790-807) -> serviceLBFlows (pipeline.go:2373-2431).
 int FeatureService::install_service_flows(const gpc_service_config& c) {
-  if (!ip_proto(c.protocol) || c.family != 4) return -GPC_EINVAL;
+  if (!ip_proto(c.protocol) || !family_ok(c.family)) return -GPC_EINVAL;
   if (c.affinity_timeout || c.is_dsr || c.is_nested || (c.is_external && c.traffic_policy_local))
     return -GPC_EINVAL;  // learn / DSR / multi-cluster / short-circuit flows: not modelled
-  const IPAddr ip = to_ip(c.ip, 4);
+  const IPAddr ip = to_ip(c.ip, c.family);
   const uint32_t gid = c.traffic_policy_local ? c.local_group_id : c.cluster_group_id;  // TrafficPolicyGroupID
   Flow f;
   f.table = TB_SERVICE_LB;
   f.priority = kPriorityNormal;
   f.cookie = cookie();
-  set_proto(f.m, ip_proto(c.protocol), 4);
+  set_proto(f.m, ip_proto(c.protocol), c.family);
   f.m.has_tp_dst = true;
   f.m.tp_dst = c.port;
   f.m.tp_dst_m = 0xffff;
@@ -222,38 +253,58 @@ int FeatureService::install_service_flows(const gpc_service_config& c) {
 }
 
 int FeatureService::uninstall_service_flows(const uint8_t* ip, uint8_t family, uint16_t port, uint8_t proto) {
-  if (!ip_proto(proto) || family != 4) return -GPC_EINVAL;
+  if (!ip_proto(proto) || !family_ok(family)) return -GPC_EINVAL;
   cached_.erase(service_key(to_ip(ip, family), port, proto));
   generation_++;
   return GPC_OK;
 }
 
 int FeatureService::install_pod(const uint8_t* ip, uint8_t family, uint32_t ofport) {
-  if (family != 4) return -GPC_EINVAL;
-  pods_[to_ip(ip, 4).v4()] = ofport;
+  if (!family_ok(family)) return -GPC_EINVAL;
+  if (family == 6) pods6_[to_ip(ip, 6)] = ofport;
+  else pods_[to_ip(ip, 4).v4()] = ofport;
   generation_++;
   return GPC_OK;
 }
 
-int FeatureService::set_node_port_addresses(const uint32_t* v4, size_t n) {
+int FeatureService::set_node_port_addresses(const uint8_t* ips, uint8_t family, size_t n) {
+  if (!family_ok(family)) return -GPC_EINVAL;
+  // cache keys: "NP" + address for IPv4, "N6" + address for IPv6 (one set per family)
+  const char* const prefix = family == 6 ? "N6" : "NP";
   for (auto it = cached_.begin(); it != cached_.end();)
-    it = it->first.compare(0, 2, "NP") == 0 ? cached_.erase(it) : std::next(it);
-  std::vector<uint32_t> addrs;
-  for (size_t i = 0; i < n; i++)
-    if ((v4[i] >> 24) != 127u) addrs.push_back(v4[i]);  // loopback: not NodePort traffic from a Pod
-  if (n) addrs.push_back(kVirtualNodePortDNAT);  // the gateway's DNATed NodePort connections
-  for (uint32_t a : addrs) {
+    it = it->first.compare(0, 2, prefix) == 0 ? cached_.erase(it) : std::next(it);
+  std::vector<IPAddr> addrs;
+  for (size_t i = 0; i < n; i++) {
+    const IPAddr a = to_ip(ips + 16 * i, family);
+    bool loopback = a.b[0] == 127;  // loopback: not NodePort traffic from a Pod
+    if (family == 6) {
+      loopback = a.b[15] == 1;
+      for (int k = 0; k < 15; k++) loopback = loopback && a.b[k] == 0;
+    }
+    if (!loopback) addrs.push_back(a);
+  }
+  if (n) {  // the gateway's DNATed NodePort connections
+    uint8_t v[16] = {0};
+    if (family == 6) std::memcpy(v, kVirtualNodePortDNAT6, 16);
+    else for (int k = 0; k < 4; k++) v[k] = uint8_t(kVirtualNodePortDNAT >> (24 - 8 * k));
+    addrs.push_back(to_ip(v, family));
+  }
+  for (const IPAddr& a : addrs) {
     Flow f;
     f.table = TB_NODEPORT_MARK;
     f.priority = kPriorityNormal;
     f.cookie = cookie();
-    set_proto(f.m, 0, 4);
+    set_proto(f.m, 0, family);
     f.m.nw_dst.set = true;
-    f.m.nw_dst.addr.fam = 4;
-    for (int k = 0; k < 4; k++) f.m.nw_dst.addr.b[k] = uint8_t(a >> (24 - 8 * k));
+    f.m.nw_dst.addr = a;
     f.acts.push_back(set_reg(4, kToNodePort, kToNodePort));
-    char key[24];
-    std::snprintf(key, sizeof key, "NP%08x", a);
+    char key[40];
+    int o = std::snprintf(key, sizeof key, "%s", prefix);
+    if (family == 6) {
+      for (int k = 0; k < 16; k++) o += std::snprintf(key + o, sizeof key - size_t(o), "%02x", a.b[k]);
+    } else {
+      std::snprintf(key + o, sizeof key - size_t(o), "%08x", a.v4());
+    }
     cached_[key] = {f};
   }
   generation_++;
@@ -261,8 +312,9 @@ int FeatureService::set_node_port_addresses(const uint32_t* v4, size_t n) {
 }
 
 int FeatureService::uninstall_pod(const uint8_t* ip, uint8_t family) {
-  if (family != 4) return -GPC_EINVAL;
-  pods_.erase(to_ip(ip, 4).v4());
+  if (!family_ok(family)) return -GPC_EINVAL;
+  if (family == 6) pods6_.erase(to_ip(ip, 6));
+  else pods_.erase(to_ip(ip, 4).v4());
   generation_++;
   return GPC_OK;
 }
@@ -331,8 +383,36 @@ struct SvcHash {  // 2-choice cuckoo table of (key, value), kSvcSlots slots per 
 
 }  // namespace
 
+// A group is an IPv6 one when a bucket loads xxreg3; a group without Endpoints belongs to no family.
+static bool group_is_v6(const Group& g) {
+  for (auto& b : g.buckets)
+    for (auto& a : b.acts)
+      if (a.kind == ACT_SET_XXREG3) return true;
+  return false;
+}
+static bool group_is_v4(const Group& g) {
+  for (auto& b : g.buckets)
+    for (auto& a : b.acts)
+      if (a.kind == ACT_SET_REG && a.a == 3) return true;
+  return false;
+}
+
+bool FeatureService::has_state(uint8_t family) const {
+  for (auto& kv : cached_)
+    for (auto& f : kv.second)
+      if ((f.m.dl_type == kEthIPv6) == (family == 6)) return true;
+  bool bare = false;  // a group without Endpoints
+  for (auto& kv : groups_) {
+    if (family == 6 ? group_is_v6(kv.second) : group_is_v4(kv.second)) return true;
+    bare |= !group_is_v6(kv.second) && !group_is_v4(kv.second);
+  }
+  // groups without Endpoints alone keep an (empty) IPv4 image, unless the state is all IPv6
+  return family == 4 && bare && !has_state(6);
+}
+
 int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) const {
   blob->clear();
+  if (!has_state(4)) return GPC_OK;
   // EndpointDNAT flows: (proto, endpoint ip, port) -> DNAT exists
   std::map<std::tuple<uint8_t, uint32_t, uint16_t>, bool> dnat;
   struct Svc {
@@ -345,6 +425,7 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
   bool any_node_port = false;
   for (auto& kv : cached_)
     for (auto& f : kv.second) {
+      if (f.m.dl_type == kEthIPv6) continue;  // build_image6
       if (f.table == TB_NODEPORT_MARK) {
         if (!f.m.nw_dst.set || f.m.nw_dst.plen >= 0) {
           *err = "unsupported NodePortMark flow: " + f.str();
@@ -381,6 +462,10 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
   for (auto& s : svcs) {
     uint32_t first = uint32_t(ep_words.size() / 4), n = 0;
     auto git = groups_.find(s.gid);
+    if (git != groups_.end() && group_is_v6(git->second)) {
+      *err = "IPv4 Service with an IPv6 Endpoint group: " + git->second.str();
+      return -GPC_EINVAL;
+    }
     if (git != groups_.end()) {
       for (auto& b : git->second.buckets) {
         uint32_t ip = 0, port = 0, flags = 0;
@@ -458,6 +543,157 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
       w[kSvcSlotWords * i] = uint32_t(k);
       w[kSvcSlotWords * i + 1] = uint32_t(k >> 32);
       w[kSvcSlotWords * i + 2] = h.vals[size_t(b) * kSvcSlots + i];
+    }
+  }
+  std::copy(svc_words.begin(), svc_words.end(), blob->begin() + hdr.svc_off);
+  std::copy(ep_words.begin(), ep_words.end(), blob->begin() + hdr.ep_off);
+  return GPC_OK;
+}
+
+int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) const {
+  blob->clear();
+  if (!has_state(6)) return GPC_OK;
+  // EndpointDNAT flows: (proto, endpoint address, port) -> DNAT exists
+  std::map<std::tuple<uint8_t, IPAddr, uint16_t>, bool> dnat;
+  struct Svc {
+    uint8_t proto;
+    uint16_t port;
+    uint32_t a[4];
+    uint32_t gid;
+    bool reg7;
+  };
+  std::vector<Svc> svcs;
+  std::vector<IPAddr> node_port_addrs;
+  bool any_node_port = false;
+  for (auto& kv : cached_)
+    for (auto& f : kv.second) {
+      if (f.m.dl_type != kEthIPv6) continue;
+      if (f.table == TB_NODEPORT_MARK) {
+        if (!f.m.nw_dst.set || f.m.nw_dst.plen >= 0) {
+          *err = "unsupported NodePortMark flow: " + f.str();
+          return -GPC_EINVAL;
+        }
+        node_port_addrs.push_back(f.m.nw_dst.addr);
+      } else if (f.table == TB_ENDPOINT_DNAT) {
+        if (!f.m.has_xxreg3 || !(f.m.reg_present & (1u << 4)) || f.acts.empty() || f.acts[0].kind != ACT_CT_DNAT6) {
+          *err = "unsupported EndpointDNAT flow: " + f.str();
+          return -GPC_EINVAL;
+        }
+        dnat[{f.m.nw_proto, to_ip(f.m.xxreg3, 6), uint16_t(f.m.reg_v[4] & 0xffffu)}] = true;
+      } else if (f.table == TB_SERVICE_LB) {
+        // a NodePort Service (ToNodePortAddressRegMark, no Service IP) is keyed by address 0
+        const bool node_port = (f.m.reg_present & (1u << 4)) && (f.m.reg_m[4] & kToNodePort) && (f.m.reg_v[4] & kToNodePort);
+        any_node_port |= node_port;
+        Svc s{f.m.nw_proto, f.m.tp_dst, {0, 0, 0, 0}, 0, false};
+        if (!node_port) words_of(f.m.nw_dst.addr.b, s.a);
+        bool grp = false;
+        for (auto& a : f.acts) {
+          if (a.kind == ACT_GROUP) s.gid = a.a, grp = true;
+          if (a.kind == ACT_SET_REG && a.a == 7) s.reg7 = true;
+        }
+        if (!grp || node_port == f.m.nw_dst.set || (f.m.nw_dst.set && f.m.nw_dst.plen >= 0) || !f.m.has_tp_dst ||
+            f.m.tp_dst_m != 0xffff) {
+          *err = "unsupported ServiceLB flow: " + f.str();
+          return -GPC_EINVAL;
+        }
+        svcs.push_back(s);
+      }
+    }
+  std::vector<uint32_t> svc_words, ep_words;
+  std::vector<std::pair<uint64_t, uint32_t>> kv;
+  for (auto& s : svcs) {
+    uint32_t first = uint32_t(ep_words.size() / kSvc6EpWords), n = 0;
+    auto git = groups_.find(s.gid);
+    if (git != groups_.end() && group_is_v4(git->second)) {
+      *err = "IPv6 Service with an IPv4 Endpoint group: " + git->second.str();
+      return -GPC_EINVAL;
+    }
+    if (git != groups_.end()) {
+      for (auto& b : git->second.buckets) {
+        IPAddr ip;
+        ip.fam = 6;
+        uint32_t port = 0, flags = 0;
+        bool noep = false, to_dnat = false;
+        for (auto& a : b.acts) {
+          if (a.kind == ACT_SET_XXREG3)
+            for (int k = 0; k < 8; k++) {
+              ip.b[k] = uint8_t(a.lv >> (56 - 8 * k));
+              ip.b[8 + k] = uint8_t(a.lm >> (56 - 8 * k));
+            }
+          if (a.kind == ACT_SET_REG && a.a == 4 && a.c == 0xffffu) port = a.b;
+          if (a.kind == ACT_SET_REG && a.a == 4 && (a.b & kRemoteEndpoint)) flags |= GPC_LB_REMOTE;
+          if (a.kind == ACT_SET_REG && a.a == 0 && (a.b & kSvcNoEp)) noep = true;
+          if (a.kind == ACT_RESUBMIT) to_dnat = a.a == TB_ENDPOINT_DNAT;
+        }
+        if (!to_dnat) {
+          *err = "unsupported group bucket (session affinity): " + git->second.str();
+          return -GPC_EINVAL;
+        }
+        if (noep) continue;
+        if (dnat.count({s.proto, ip, uint16_t(port)})) flags |= GPC_LB_DNAT;
+        uint32_t out_port = 0, dest = GPC_DEST_GATEWAY;
+        auto pit = pods6_.find(ip);
+        if (pit != pods6_.end()) {
+          out_port = pit->second;
+          dest = GPC_DEST_POD;
+        } else if (flags & GPC_LB_REMOTE) {
+          dest = GPC_DEST_TUNNEL;
+        }
+        uint32_t w[4];
+        words_of(ip.b, w);
+        ep_words.insert(ep_words.end(), {w[0], w[1], w[2], w[3], port | (flags << 16), out_port, dest, 0u});
+        n++;
+      }
+    }
+    uint32_t lg = 6;
+    while ((1u << lg) < n) lg++;
+    if (n >= (1u << 24)) {
+      *err = "too many Endpoints in one group";
+      return -GPC_EINVAL;
+    }
+    kv.push_back({svc6_hash_key(s.proto, s.a, s.port), uint32_t(svc_words.size() / 4)});
+    svc_words.insert(svc_words.end(), {first, n | (lg << 24), s.gid, s.reg7 ? kSvcLoadReg7 : 0u});
+  }
+  SvcHash h;
+  if (!h.build(kv)) {
+    *err = "Service hash construction failed";
+    return -GPC_ENOMEM;
+  }
+  const uint32_t nb = 1u << h.log2;
+  SvcHdr hdr{};
+  hdr.map_log2 = 12;
+  while (hdr.map_log2 < 22 && (1ull << hdr.map_log2) < 16ull * kv.size()) hdr.map_log2++;
+  hdr.map_off = 32;
+  hdr.hash_off = hdr.map_off + (1u << (hdr.map_log2 - 5));
+  hdr.hash_log2 = h.log2;
+  hdr.svc_off = hdr.hash_off + nb * kSvc6BucketWords;
+  hdr.n_svc = uint32_t(svc_words.size() / 4);
+  hdr.ep_off = hdr.svc_off + uint32_t(svc_words.size());
+  hdr.n_ep = uint32_t(ep_words.size() / kSvc6EpWords);
+  if (!any_node_port) node_port_addrs.clear();
+  if (node_port_addrs.size() > kSvcMaxNodePortAddrs) {
+    *err = "too many NodePort addresses";
+    return -GPC_EINVAL;
+  }
+  hdr.np_off = hdr.ep_off + uint32_t(ep_words.size());
+  hdr.n_np = uint32_t(node_port_addrs.size());
+  blob->assign(hdr.np_off + 4 * node_port_addrs.size(), 0u);
+  for (size_t i = 0; i < node_port_addrs.size(); i++) words_of(node_port_addrs[i].b, blob->data() + hdr.np_off + 4 * i);
+  std::memcpy(blob->data(), &hdr, sizeof hdr);
+  for (auto& e : kv) {
+    const uint32_t mb = svc_map_bit(e.first, hdr.map_log2);
+    (*blob)[hdr.map_off + (mb >> 5)] |= 1u << (mb & 31u);
+  }
+  for (uint32_t b = 0; b < nb; b++) {
+    uint32_t* w = blob->data() + hdr.hash_off + size_t(b) * kSvc6BucketWords;
+    for (uint32_t i = 0; i < kSvcSlots; i++) {
+      if (!h.keys[size_t(b) * kSvcSlots + i]) continue;  // an empty slot: tag word 0 never matches
+      const uint32_t si = h.vals[size_t(b) * kSvcSlots + i];
+      const Svc& s = svcs[si];
+      uint32_t* slot = w + kSvc6SlotWords * i;
+      for (int k = 0; k < 4; k++) slot[k] = s.a[k];
+      slot[4] = svc6_tag(s.proto, s.port);
+      slot[5] = si;
     }
   }
   std::copy(svc_words.begin(), svc_words.end(), blob->begin() + hdr.svc_off);

@@ -24,8 +24,10 @@ class FeatureService {
   int uninstall_service_flows(const uint8_t* ip, uint8_t family, uint16_t port, uint8_t proto);
   int install_pod(const uint8_t* ip, uint8_t family, uint32_t ofport);
   // NodePort addresses (NewClient's nodePortAddressesIPv4 with proxyAll): the NodePortMark flows
-  // (pipeline.go:2282-2314) for each non-loopback address and the virtual NodePort DNAT IP
-  int set_node_port_addresses(const uint32_t* v4, size_t n);
+  // (pipeline.go:2282-2314) for each non-loopback address and the virtual NodePort DNAT IP. One set
+  // per family (featureService.nodePortAddresses[ipProtocol]): a call replaces its family's flows.
+  // `ips`: n addresses of 16 bytes each (an IPv4 address in the first 4)
+  int set_node_port_addresses(const uint8_t* ips, uint8_t family, size_t n);
   int uninstall_pod(const uint8_t* ip, uint8_t family);
 
   std::string dump_flows() const;   // FlowModToString lines of the realized Service flows
@@ -35,7 +37,12 @@ class FeatureService {
 
   // Device Service image (core.hpp "Service image"), IPv4. Returns -GPC_EINVAL with *err for a
   // realized flow shape the data path does not implement.
+  // Empty blob: no IPv4 Service state.
   int build_image(std::vector<uint32_t>* blob, std::string* err) const;
+  // The IPv6 Service image (core.hpp "IPv6 Service image") from the tcp6 / udp6 / sctp6 ServiceLB
+  // flows, the xxreg3 groups, the IPv6 EndpointDNAT / NodePortMark flows and the IPv6 Pod map.
+  // Empty blob: no IPv6 Service state.
+  int build_image6(std::vector<uint32_t>* blob, std::string* err) const;
 
  private:
   uint64_t cookie() const;
@@ -45,6 +52,9 @@ class FeatureService {
   std::map<std::string, std::vector<Flow>> cached_;  // featureService.cachedFlows: cache key -> flows
   std::map<uint32_t, Group> groups_;                 // featureService.groupCache
   std::map<uint32_t, uint32_t> pods_;                // IPv4 Pod IP -> ofport
+  std::map<IPAddr, uint32_t> pods6_;                 // IPv6 Pod IP -> ofport
+  bool family_ok(uint8_t family) const { return family == 4 || (family == 6 && cfg_.ipv6_enabled); }
+  bool has_state(uint8_t family) const;              // some flow or group of that family is realized
   uint64_t generation_ = 0;
 };
 

@@ -36,6 +36,9 @@ GROUP_KEY_AUTO, GROUP_KEY_ADDR, GROUP_KEY_SCAN = 0, 1, 2  # gpc_group_key
 
 LB_DTYPE = np.dtype([("endpoint_ip", "<u4"), ("endpoint_port", "<u2"), ("flags", "u1"), ("reserved", "u1"),
                      ("group_id", "<u4"), ("out_port", "<u4")])
+# gpc_lb_result6 (32 B): endpoint_ip = 16 network-order bytes
+LB6_DTYPE = np.dtype([("endpoint_ip", "u1", (16,)), ("endpoint_port", "<u2"), ("flags", "u1"), ("reserved", "u1"),
+                      ("group_id", "<u4"), ("out_port", "<u4"), ("reserved2", "<u4")])
 LB_HIT, LB_NO_ENDPOINT, LB_DNAT, LB_REMOTE = 1, 2, 4, 8
 VFLAG_PASS, VFLAG_TIE, VFLAG_PACKETIN = 1, 2, 4  # gpc_verdict.flags
 VTABLE_ENDPOINT_DNAT = 4
@@ -131,7 +134,8 @@ EXPORTS = ["gpc_create", "gpc_destroy", "gpc_initialize", "gpc_install_rule", "g
            "gpc_abi_version", "gpc_set_node_port_addresses", "gpc_classify6", "gpc_classify6_host", "gpc_debug_image6", "gpc_new_dns_conjunction",
            "gpc_add_dns_conj_addrs", "gpc_del_dns_conj_addrs", "gpc_network_policy_flow_keys", "gpc_stream_epoch", "gpc_trace", "gpc_replay",
            "gpc_set_launch_timing", "gpc_launch_times", "gpc_create_multi", "gpc_n_devices", "gpc_classify_on",
-           "gpc_classify6_on", "gpc_classify_host_on", "gpc_counters_on", "gpc_debug_epoch6", "gpc_debug_fail_uploads"]
+           "gpc_classify6_on", "gpc_classify_host_on", "gpc_counters_on", "gpc_debug_epoch6", "gpc_debug_fail_uploads",
+           "gpc_classify6_lb", "gpc_classify6_lb_on", "gpc_classify6_host_lb", "gpc_debug_service_image6"]
 
 _lib = None
 
@@ -193,6 +197,10 @@ def load(path: str = LIB_PATH):
     lib.gpc_debug_service_image.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(sz)]
     lib.gpc_classify6.argtypes = [vp, C.POINTER(gpc_pkt_soa), sz, vp, i32, vp]
     lib.gpc_classify6_host.argtypes = [vp, C.POINTER(gpc_pkt_soa), sz, vp, i32]
+    lib.gpc_classify6_lb.argtypes = [vp, C.POINTER(gpc_pkt_soa), sz, vp, vp, i32, vp]
+    lib.gpc_classify6_lb_on.argtypes = [vp, C.c_uint32, C.POINTER(gpc_pkt_soa), sz, vp, vp, i32, vp]
+    lib.gpc_classify6_host_lb.argtypes = [vp, C.POINTER(gpc_pkt_soa), sz, vp, vp, i32]
+    lib.gpc_debug_service_image6.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(sz)]
     lib.gpc_debug_image6.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
     lib.gpc_new_dns_conjunction.argtypes = [vp, C.c_uint32]
     lib.gpc_add_dns_conj_addrs.argtypes = [vp, C.c_uint32, C.POINTER(gpc_addr), sz]
@@ -581,16 +589,16 @@ class Classifier:
         fam, b = _ip_bytes(ip)
         _check(self.lib.gpc_uninstall_pod(self.h, b, fam), "UninstallPodFlows")
 
-    def set_node_port_addresses(self, ips):
-        """NewClient's nodePortAddressesIPv4 with proxyAll (pipeline.go:2282-2314 nodePortMarkFlows);
-        [] turns NodePort marking off."""
+    def set_node_port_addresses(self, ips, family=4):
+        """NewClient's nodePortAddressesIPv4 / IPv6 with proxyAll (pipeline.go:2282-2314
+        nodePortMarkFlows): the set of one family; [] turns that family's NodePort marking off."""
         buf = (C.c_uint8 * (16 * max(1, len(ips))))()
         for i, ip in enumerate(ips):
             fam, b = _ip_bytes(ip)
-            if fam != 4:
-                raise GpcError(-GPC_EINVAL, "NodePort addresses: IPv4 only")
-            C.memmove(C.byref(buf, 16 * i), b, 4)
-        _check(self.lib.gpc_set_node_port_addresses(self.h, buf, 4, len(ips)), "gpc_set_node_port_addresses")
+            if fam != family:
+                raise GpcError(-GPC_EINVAL, "NodePort addresses: not of family %d" % family)
+            C.memmove(C.byref(buf, 16 * i), b, 16)
+        _check(self.lib.gpc_set_node_port_addresses(self.h, buf, family, len(ips)), "gpc_set_node_port_addresses")
 
     def dump_groups(self) -> List[str]:
         need = C.c_size_t()
@@ -603,6 +611,12 @@ class Classifier:
         b = C.POINTER(C.c_uint32)()
         n = C.c_size_t()
         _check(self.lib.gpc_debug_service_image(self.h, C.byref(b), C.byref(n)), "gpc_debug_service_image")
+        return C.cast(b, C.c_void_p).value
+
+    def debug_service_image6(self):
+        b = C.POINTER(C.c_uint32)()
+        n = C.c_size_t()
+        _check(self.lib.gpc_debug_service_image6(self.h, C.byref(b), C.byref(n)), "gpc_debug_service_image6")
         return C.cast(b, C.c_void_p).value
 
     # --- data path
@@ -631,12 +645,15 @@ class Classifier:
                                              lbo.ctypes.data if lb else None, int(count)), "gpc_classify_host")
         return (out.reshape(n, 2), lbo) if lb else out.reshape(n, 2)
 
-    def classify6_host(self, cols: Dict[str, np.ndarray], count=False):
-        """IPv6 verdicts (n, 2): cols carries src6 / dst6 as (n, 16) uint8 (network order)."""
+    def classify6_host(self, cols: Dict[str, np.ndarray], count=False, lb=False):
+        """IPv6 verdicts (n, 2): cols carries src6 / dst6 as (n, 16) uint8 (network order); with
+        lb=True also the Service stage results (n,) of LB6_DTYPE."""
         soa, keep, n = pkt_soa_host(cols)
         out = np.zeros(2 * n, dtype=VERDICT_DTYPE)
-        _check(self.lib.gpc_classify6_host(self.h, C.byref(soa), n, out.ctypes.data, int(count)), "gpc_classify6_host")
-        return out.reshape(n, 2)
+        lbo = np.zeros(n, dtype=LB6_DTYPE) if lb else None
+        _check(self.lib.gpc_classify6_host_lb(self.h, C.byref(soa), n, out.ctypes.data, lbo.ctypes.data if lb else None,
+                                              int(count)), "gpc_classify6_host")
+        return (out.reshape(n, 2), lbo) if lb else out.reshape(n, 2)
 
     def classify6_device(self, soa: gpc_pkt_soa, n: int, out_ptr: int, count=False, stream: int = 0, slot=0):
         _check(self.lib.gpc_classify6_on(self.h, int(slot), C.byref(soa), n, out_ptr, int(count), stream or None),

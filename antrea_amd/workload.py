@@ -309,14 +309,15 @@ def add_services(wl: Workload, n_services: int, eps_per_service: int, seed=RULE_
 def install_services(clf, wl: Workload):
     """The AntreaProxy calls for wl's Services (client.go:710-815 order: groups, Endpoint flows,
     Service flows) plus the Pod map."""
+    fam = (6,) if getattr(wl, "svc_family", 4) == 6 else ()  # (services_to_ipv6)
     for ip, port in wl.pods.items():
         clf.install_pod(_ip(ip), port)
     if getattr(wl, "node_port_addresses", None):
-        clf.set_node_port_addresses(wl.node_port_addresses)
+        clf.set_node_port_addresses(wl.node_port_addresses, *fam)
     for gid, eps in wl.groups.items():
         clf.install_service_group(gid, eps)
     for proto, eps in wl.endpoint_flows:
-        clf.install_endpoint_flows(proto, eps)
+        clf.install_endpoint_flows(proto, eps, *fam)
     for cfg in wl.services:
         clf.install_service_flows(cfg)
 
@@ -529,4 +530,35 @@ def packets_to_v6_torch(cols, embed="96"):
         out[k + "6"] = z.to(torch.uint8).contiguous()
     p = cols["proto"]
     out["proto"] = torch.where(p == 1, torch.full_like(p, 58), p)
+    return out
+
+
+VIRTUAL_NODE_PORT_DNAT6 = "fc01::aabb:ccdd:eefe"  # config.VirtualNodePortDNATIPv6
+
+
+def services_to_ipv6(wl: Workload, embed="96") -> Workload:
+    """An add_services workload in IPv6: rules through to_ipv6, Service IPs, Endpoints, Pods and
+    NodePort addresses through the same embedding; NodePort Services take the IPv6 virtual NodePort
+    DNAT IP. Its packets: gen_packets(wl, ...) of the IPv4 workload, then service_packets_to_v6."""
+    import copy
+    out = to_ipv6(wl, embed=embed)
+    e = lambda a: _v6_addr(a, embed)
+    ep6 = lambda eps: [dict(x, ip=e(x["ip"])) for x in eps]
+    out.svc_family = 6
+    out.services = [dict(s, ip=VIRTUAL_NODE_PORT_DNAT6 if s.get("is_nodeport") else e(s["ip"])) for s in wl.services]
+    out.groups = {g: ep6(eps) for g, eps in wl.groups.items()}
+    out.endpoint_flows = [(p, ep6(eps)) for p, eps in wl.endpoint_flows]
+    out.pods = {v6_embed(int(ip), embed): port for ip, port in wl.pods.items()}
+    if getattr(wl, "node_port_addresses", None):
+        out.node_port_addresses = [e(a) for a in wl.node_port_addresses]
+    out.svc_meta, out.svc_frac = copy.copy(wl.svc_meta), wl.svc_frac
+    return out
+
+
+def service_packets_to_v6(cols: Dict[str, np.ndarray], embed="96") -> Dict[str, np.ndarray]:
+    """packets_to_v6 for a services_to_ipv6 workload: packets addressed to the IPv4 virtual NodePort
+    DNAT IP go to the IPv6 one."""
+    out = packets_to_v6(cols, embed)
+    virt = np.asarray(cols["dst"]) == int(ipaddress.ip_address(VIRTUAL_NODE_PORT_DNAT))
+    out["dst6"][virt] = np.frombuffer(ipaddress.ip_address(VIRTUAL_NODE_PORT_DNAT6).packed, np.uint8)
     return out

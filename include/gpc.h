@@ -268,6 +268,16 @@ typedef struct gpc_lb_result {
                                     serviceNoEndpointFlow -> SvcReject packet-in)               */
 #define GPC_LB_DNAT 0x4          /* an EndpointDNAT flow rewrote the destination               */
 #define GPC_LB_REMOTE 0x8        /* RemoteEndpointRegMark: the Endpoint is on another Node      */
+/* The same for an IPv6 packet (optional output of gpc_classify6_lb), 32 bytes, 16-byte aligned. */
+typedef struct gpc_lb_result6 {
+  uint8_t endpoint_ip[16];       /* selected Endpoint (xxreg3), network byte order; 0 if none */
+  uint16_t endpoint_port;        /* reg4[0..15]                                               */
+  uint8_t flags;                 /* GPC_LB_*                                                  */
+  uint8_t reserved;
+  uint32_t group_id;             /* Service group (reg7 ServiceGroupIDField)                   */
+  uint32_t out_port;             /* reg1 after L3Forwarding to the Endpoint (local Pod ofport) */
+  uint32_t reserved2;
+} gpc_lb_result6;
 /* gpc_verdict.table value of the egress verdict of a packet rejected by EndpointDNAT (no Endpoint). */
 #define GPC_VTABLE_ENDPOINT_DNAT 4
 
@@ -406,7 +416,12 @@ int gpc_uninstall_endpoint_flows(gpc_ctx* ctx, uint8_t protocol, uint8_t family,
  * policy) without session affinity, DSR, multi-cluster nesting or the external + Local
  * short-circuit; other configs -GPC_EINVAL. A NodePort Service (is_nodeport; the caller passes the
  * virtual NodePort DNAT IP 169.254.0.252 as its ip, as the proxier does) matches packets to the
- * NodePort addresses (gpc_set_node_port_addresses) by protocol and port (pipeline.go:2381-2387). */
+ * NodePort addresses (gpc_set_node_port_addresses) by protocol and port (pipeline.go:2381-2387).
+ * Both families take the same shapes: a family-6 config, Endpoint or Pod realizes the tcp6 / udp6 /
+ * sctp6 flows with ipv6_dst, xxreg3 (group buckets, EndpointDNAT match), zone 65510 and
+ * nat(dst=[addr]:port) (pipeline.go:2502-2528, 2582-2584); the virtual NodePort DNAT IP of family 6
+ * is fc01::aabb:ccdd:eefe. Family 6 needs gpc_config.ipv6_enabled (else -GPC_EINVAL: nothing could
+ * classify against it). */
 int gpc_install_service_flows(gpc_ctx* ctx, const gpc_service_config* cfg);
 /* UninstallServiceFlows(svcIP, svcPort, protocol) error                     client.go:809 */
 int gpc_uninstall_service_flows(gpc_ctx* ctx, const uint8_t* ip, uint8_t family, uint16_t port, uint8_t protocol);
@@ -417,8 +432,10 @@ int gpc_uninstall_pod(gpc_ctx* ctx, const uint8_t* ip, uint8_t family);
 /* NodePort addresses of the Node (NewClient nodePortAddressesIPv4 with proxyAll; ABI 6): one
  * NodePortMark flow per non-loopback address plus the virtual NodePort DNAT IP 169.254.0.252
  * (pipeline.go:2282-2314), loading ToNodePortAddressRegMark (reg4[19]) for the ServiceLB NodePort
- * flows. `ips`: n IPv4 addresses of 16 bytes each (the address in the first 4); family 4 only;
- * n = 0 removes them (proxyAll off). Replaces the previous set. */
+ * flows. `ips`: n addresses of 16 bytes each (an IPv4 address in the first 4). One set per family
+ * (featureService.nodePortAddresses[ipProtocol]): a call replaces the previous set of its family
+ * and leaves the other family's flows alone; n = 0 removes them (proxyAll off). Family 6: ::1 is
+ * skipped, the virtual IP is fc01::aabb:ccdd:eefe. */
 int gpc_set_node_port_addresses(gpc_ctx* ctx, const uint8_t* ips, uint8_t family, size_t n);
 /* ovs-ofctl dump-groups style text of the realized groups, '\n' separated. */
 int gpc_dump_groups(gpc_ctx* ctx, char* buf, size_t cap, size_t* needed);
@@ -475,10 +492,23 @@ int gpc_trace(gpc_ctx* ctx, const gpc_pkt_soa* pkt, gpc_verdict* out, gpc_lb_res
  * epoch (the IPv6 base plus a journal of the changed rules; new prefixes are interned into the
  * prefix tree in place and their LPM entries go to the journal's overflow table) and falls back
  * to a full IPv6 rebuild for a new prefix length, a prefix that is not a leaf of the tree, or a
- * journal past its size thresholds (rules, pool words, overflow entries). No AntreaProxy stage for
- * IPv6. Same verdict / counter layout. -GPC_EINVAL if the IPv6 prefixes of the rule set need more
+ * journal past its size thresholds (rules, pool words, overflow entries). Same verdict / counter
+ * layout. When IPv6 Services are committed the AntreaProxy stage runs first, on the 128-bit
+ * addresses: packets to an IPv6 Service / NodePort are load-balanced (bucket: the IPv4 hash over the
+ * XOR of each address's four 32-bit words), DNATed, and classified with ipv6_dst / tp_dst = the
+ * Endpoint, ct_ipv6_dst = the original destination (unless ct_dst6 is given), reg7, reg1 and the
+ * destination from the IPv6 Pod map; a Service without Endpoints is rejected as in gpc_classify_lb.
+ * Without IPv6 Services the launches are those of a context that never had any. -GPC_EINVAL if the IPv6 prefixes of the rule set need more
  * than 32 code bits (core.hpp). */
 int gpc_classify6(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out, int32_t count, void* stream);
+/* gpc_classify6 with the Service stage's selection in lb_out (device, n entries, 16-byte aligned,
+ * may be NULL; all zero for a packet that hit no Service). */
+int gpc_classify6_lb(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
+                     int32_t count, void* stream);
+int gpc_classify6_lb_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out,
+                        gpc_lb_result6* lb_out, int32_t count, void* stream);
+int gpc_classify6_host_lb(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
+                          int32_t count);
 /* The data path on device slot `slot` of a gpc_create_multi context: pkts / out / lb_out live on
  * that slot's device and `stream` belongs to it (NULL: its null stream). gpc_classify* == slot 0. */
 int gpc_classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out,
@@ -516,6 +546,8 @@ int gpc_debug_image(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words, const 
 int gpc_debug_image6(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words, const void** hdr, size_t* hdr_bytes);
 /* The host copy of the committed Service image (NULL / 0 when no Services). */
 int gpc_debug_service_image(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words);
+/* The same for the IPv6 Service image (NULL / 0 when no IPv6 Services). */
+int gpc_debug_service_image6(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words);
 /* Host mirror of the journal pool and the current epoch's journal header offset (NULL / 0 when
  * the epoch is the base image alone). */
 int gpc_debug_epoch(gpc_ctx* ctx, const uint32_t** pool, size_t* pool_words, uint32_t* jhdr);

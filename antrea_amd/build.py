@@ -9,7 +9,9 @@ snapshot (it is not listed in .gpurunignore).
 
 Rebuilds are decided by content, not mtime: every object carries a stamp file with the SHA-256 of
 its compile command, source and headers, so a snapshot whose sources differ from the ones a
-travelling .so was built from is rebuilt, and one that matches is not.
+travelling .so was built from is rebuilt, and one that matches is not. The library carries a second
+stamp over every compile command, source and header, so a tree that holds the library built from
+exactly these sources but not the objects (a copy without intermediate files) compiles nothing.
 """
 from __future__ import annotations
 
@@ -69,6 +71,16 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", defines
     os.makedirs(OUT, exist_ok=True)
     hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(ROOT, "include", "gpc.h")]
     objs = []
+    lib = os.path.join(OUT, "libgpc_%s.so" % variant) if variant else LIB
+    # the whole build's inputs: with the library and this stamp in place nothing is compiled
+    # (no paths in it: the tree may lie elsewhere than where the library was built)
+    whole = ["build", variant, ARCH] + list(defines) + [f for f in CXXFLAGS if not f.startswith("-I")] + HOST_SRCS + HIP_SRCS
+    all_srcs = [os.path.join(CSRC, s) for s in HOST_SRCS + HIP_SRCS] + hdrs
+    src_stamp = lib + ".src"
+    if not force and not _stale(src_stamp, whole, all_srcs) and os.path.exists(lib):
+        if verbose:
+            print(lib)
+        return lib
     for s in HOST_SRCS:
         src = os.path.join(CSRC, s)
         obj = os.path.join(OUT, s + ".o")
@@ -88,11 +100,13 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", defines
             _run(cmd)
             _stamp(obj, cmd, [src] + hdrs)
         objs.append(obj)
-    lib = os.path.join(OUT, "libgpc_%s.so" % variant) if variant else LIB
     cmd = [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs
     if force or _stale(lib, cmd, objs):
         _run(cmd)
         _stamp(lib, cmd, objs)
+    with open(src_stamp, "wb") as f:  # (the file _stale / _stamp pair with: <lib>.src + .sha256)
+        f.write(b"")
+    _stamp(src_stamp, whole, all_srcs)
     if verbose:
         print(lib)
     return lib

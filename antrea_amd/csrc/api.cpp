@@ -6,6 +6,7 @@
 #include <atomic>
 #include <deque>
 #include <chrono>
+#include <ctime>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -98,6 +99,7 @@ struct DevImage {  // one uploaded image (freed when the last epoch using it ret
   uint8_t sort_table[2] = {0, 0};       // per policy stage: the table whose scan length orders lanes
   uint32_t axes = 0;                    // axes read by the sub-indexes (group_axes)
   bool composite = false;               // some table has a composite driver index (TableHdr n_cidx)
+  bool affinity = false;                // a Service image with session-affinity Services (SvcHdr n_aff)
   ~DevImage() {
     int cur = 0;
     const bool swap = hipGetDevice(&cur) == hipSuccess && cur != device;
@@ -153,6 +155,15 @@ struct DevState {
   uint32_t counter_copies = 1;                   // striped copies of the counter array (counter_copies_for)
   std::vector<LaunchMarks> marks;                // gpc_set_launch_timing event sets (data)
   size_t marks_next = 0, marks_used = 0, marks_dropped = 0;
+  // Session-affinity table of the slot (gpc_config.session_affinity; core.hpp "Affinity table"):
+  // allocated and reset by the first batch against an image with affinity Services, kept over
+  // commits, dropped with the slot's other buffers by gpc_replay. All under `data`.
+  uint32_t* d_aff = nullptr;
+  unsigned long long* d_aff_ctr = nullptr;       // AffCounter array
+  uint32_t aff_seq = 0;                          // launch sequence of the last affinity batch
+  uint32_t aff_swept = 0;                        // clock value of the last sweep
+  uint64_t aff_sweeps = 0;
+  hipEvent_t aff_done = nullptr;                 // after the last table kernel queued on the slot
 };
 
 // Delta commits append the changed rules to the journal of the current base (image.hpp Journal).
@@ -252,6 +263,9 @@ struct gpc_ctx {
   bool comp_pending = false;             // a background compaction was requested, not installed yet
   std::vector<std::pair<uint64_t, FeatureNP::Dirty>> dirty_hist;  // per commit since the request
   Compactor comp;
+  // Session-affinity clock (gpc_set_affinity_clock; `data`): seconds, monotonic; never set: CLOCK_MONOTONIC
+  bool aff_clock_set = false;
+  uint32_t aff_clock = 0;
   void* stage6 = nullptr;                // pinned staging buffer of IPv6 journal uploads
   size_t stage6_bytes = 0;
   gpc_ctx(const gpc_config& c, const std::vector<int>& devices) : cfg(c), np(c), svc(c), dev(devices.size()) {
@@ -480,6 +494,10 @@ static int upload_words(const std::vector<uint32_t>& w, int device, hipStream_t 
   return GPC_OK;
 }
 
+static bool svc_has_affinity(const std::vector<uint32_t>& blob) {
+  return blob.size() * 4 >= sizeof(SvcHdr) && reinterpret_cast<const SvcHdr*>(blob.data())->n_aff != 0;
+}
+
 static void collect_retired(DevState& D, bool wait) {  // the slot's device is current
   if (wait && !D.retired.empty()) (void)hipDeviceSynchronize();
   size_t k = 0;
@@ -676,6 +694,7 @@ int gpc_create_multi(const gpc_config* cfg, const int32_t* devices, size_t n, gp
   if (!cfg || !out || !devices || n == 0 || n > GPC_MAX_DEVICES) return -GPC_EINVAL;
   if (!cfg->ipv4_enabled && !cfg->ipv6_enabled) return -GPC_EINVAL;
   if (cfg->group_key < GPC_GROUP_KEY_AUTO || cfg->group_key > GPC_GROUP_KEY_SCAN) return -GPC_EINVAL;
+  if (cfg->session_affinity && (cfg->session_affinity < 8 || cfg->session_affinity > 26)) return -GPC_EINVAL;
   for (size_t k = 0; k < n; k++)
     if (devices[k] < 0) return -GPC_EINVAL;
   try {
@@ -699,6 +718,14 @@ static void drop_slot(DevState& D) {
   collect_retired(D, true);
   if (D.d_counters) (void)hipFree(D.d_counters);
   D.d_counters = nullptr;
+  if (D.d_aff) (void)hipFree(D.d_aff);
+  if (D.d_aff_ctr) (void)hipFree(D.d_aff_ctr);
+  if (D.aff_done) (void)hipEventDestroy(D.aff_done);
+  D.d_aff = nullptr;
+  D.d_aff_ctr = nullptr;
+  D.aff_done = nullptr;
+  D.aff_seq = D.aff_swept = 0;
+  D.aff_sweeps = 0;
   for (auto& kv : D.scratch) {
     (void)hipFree(kv.second.p);
     if (kv.second.done) (void)hipEventDestroy(kv.second.done);
@@ -718,7 +745,7 @@ void gpc_destroy(gpc_ctx* ctx) {
   ctx->comp.cv.notify_all();
   if (ctx->comp.th.joinable()) ctx->comp.th.join();
   for (DevState& D : ctx->dev) {
-    if (D.cur.base || D.d_counters || !D.retired.empty() || D.ustream || !D.marks.empty()) {
+    if (D.cur.base || D.d_counters || !D.retired.empty() || D.ustream || !D.marks.empty() || D.d_aff) {
       (void)hipSetDevice(D.device);
       (void)hipDeviceSynchronize();
       drop_slot(D);
@@ -1054,6 +1081,12 @@ int gpc_replay(gpc_ctx* ctx) {
       D.launch_epoch.clear();
       old[k].scratch.swap(D.scratch);
       old[k].retired.swap(D.retired);
+      // the affinity table goes with the device state: a reset loses learned flows as an OVS restart does
+      std::swap(old[k].d_aff, D.d_aff);
+      std::swap(old[k].d_aff_ctr, D.d_aff_ctr);
+      std::swap(old[k].aff_done, D.aff_done);
+      D.aff_seq = D.aff_swept = 0;
+      D.aff_sweeps = 0;
       old[k].ustream = D.ustream;
     }
     ctx->cur_epoch = 0;
@@ -1105,6 +1138,7 @@ int gpc_replay(gpc_ctx* ctx) {
       }
     }
     if (!rc && !ctx->svc_blob.empty()) rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc);
+    if (!rc && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
     if (!rc && !ctx->svc6_blob.empty()) rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6);
     if (!rc && (hip_ok(hipMalloc(&nc[k], cap * kCounterBytes * (copies + 1))) ||
                 hip_ok(hipMemset(nc[k], 0, cap * kCounterBytes * (copies + 1)))))
@@ -1213,6 +1247,131 @@ static uint32_t group_key(const gpc_ctx* ctx) {
   return (b.sort_table[0] || b.sort_table[1]) ? uint32_t(GPC_GROUP_KEY_SCAN) : uint32_t(GPC_GROUP_KEY_ADDR);
 }
 
+constexpr size_t kAffCtrBytes = size_t(kAffCounterStripes) * kAffCounters * sizeof(unsigned long long);
+
+static uint32_t aff_now(const gpc_ctx* ctx) {  // ctx->data held
+  if (ctx->aff_clock_set) return ctx->aff_clock;
+  timespec ts{};
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return uint32_t(ts.tv_sec);
+}
+
+static AffTable aff_table(const gpc_ctx* ctx, const DevState& D) {
+  return AffTable{D.d_aff, uint32_t(ctx->cfg.session_affinity), D.d_aff_ctr};
+}
+
+// The slot's affinity table for a batch on stream st (ctx->data held, the slot's device current):
+// allocated and reset on first use; the batch waits for the table kernels of the batch before it
+// (whatever stream that ran on) and gets the next launch sequence; expired entries are swept when
+// the clock has moved since the last sweep, so a learn pass never meets a dead entry and their
+// slots are free for it. Fills al->tab / now / seq / done.
+static int aff_prepare(gpc_ctx* ctx, DevState& D, hipStream_t st, LaunchMarks* marks, AffLaunch* al) {
+  const uint32_t now = aff_now(ctx);
+  const bool fresh = !D.d_aff;
+  if (fresh) {
+    const size_t bytes = (size_t(kAffSlotWords) * 4) << ctx->cfg.session_affinity;
+    if (hip_ok(hipMalloc((void**)&D.d_aff, bytes))) {
+      (void)hipGetLastError();
+      D.d_aff = nullptr;
+      return -GPC_ENOMEM;
+    }
+    if ((!D.d_aff_ctr && (hip_ok(hipMalloc((void**)&D.d_aff_ctr, kAffCtrBytes)) || hip_ok(hipMemset(D.d_aff_ctr, 0, kAffCtrBytes)))) ||
+        (!D.aff_done && hip_ok(hipEventCreateWithFlags(&D.aff_done, hipEventDisableTiming)))) {
+      (void)hipFree(D.d_aff);  // (the next batch starts over: a table is only ever used after its reset)
+      D.d_aff = nullptr;
+      return -GPC_EDEV;
+    }
+    D.aff_seq = 0;
+  } else if (hip_ok(hipStreamWaitEvent(st, D.aff_done, 0))) {
+    return -GPC_EDEV;
+  }
+  const AffTable t = aff_table(ctx, D);
+  if (fresh) {
+    if (const int rc = launch_aff_sweep(t, now, kAffSweepReset, st, nullptr)) {
+      (void)hipFree(D.d_aff);
+      D.d_aff = nullptr;
+      return rc;
+    }
+    D.aff_swept = now;
+  } else if (D.aff_seq >= 0xfffffffeu) {  // the sequence wraps: the bid words start over
+    if (const int rc = launch_aff_sweep(t, now, kAffSweepBids, st, nullptr)) return rc;
+    D.aff_seq = 0;
+  }
+  if (!fresh && now > D.aff_swept) {
+    if (const int rc = launch_aff_sweep(t, now, kAffSweepExpired, st, marks)) return rc;
+    D.aff_swept = now;
+    D.aff_sweeps++;
+  }
+  al->tab = t;
+  al->now = now;
+  al->seq = ++D.aff_seq;
+  al->read_only = 0;
+  al->lb_scratch = nullptr;
+  al->done = D.aff_done;
+  return GPC_OK;
+}
+
+int gpc_set_affinity_clock(gpc_ctx* ctx, uint32_t seconds) {
+  if (!ctx) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> d(ctx->data);
+  if (ctx->aff_clock_set && seconds < ctx->aff_clock) return -GPC_EINVAL;
+  ctx->aff_clock_set = true;
+  ctx->aff_clock = seconds;
+  return GPC_OK;
+}
+
+int gpc_affinity_stats(gpc_ctx* ctx, uint32_t slot, gpc_affinity_counts* out) {
+  if (!ctx || !out || slot >= ctx->dev.size()) return -GPC_EINVAL;
+  *out = gpc_affinity_counts{};
+  if (!ctx->cfg.session_affinity) return GPC_OK;
+  out->slots = uint64_t(1) << ctx->cfg.session_affinity;
+  std::lock_guard<std::mutex> d(ctx->data);
+  DevState& D = ctx->dev[slot];
+  if (!D.d_aff) return GPC_OK;
+  if (hip_ok(hipSetDevice(D.device)) || hip_ok(hipDeviceSynchronize())) return -GPC_EDEV;
+  unsigned long long c[kAffCounters] = {}, all[kAffCounterStripes][kAffCounters];
+  if (hip_ok(hipMemset2D(D.d_aff_ctr + kAffLive, kAffCounters * sizeof(unsigned long long), 0, sizeof(unsigned long long),
+                         kAffCounterStripes)))
+    return -GPC_EDEV;
+  if (const int rc = launch_aff_sweep(aff_table(ctx, D), aff_now(ctx), kAffSweepCount, nullptr, nullptr)) return rc;
+  if (hip_ok(hipDeviceSynchronize()) || hip_ok(hipMemcpy(all, D.d_aff_ctr, sizeof all, hipMemcpyDeviceToHost))) return -GPC_EDEV;
+  for (auto& stripe : all)
+    for (uint32_t k = 0; k < kAffCounters; k++) c[k] += stripe[k];
+  out->live = c[kAffLive];
+  out->learned = c[kAffLearned];
+  out->hits = c[kAffHits];
+  out->overflow = c[kAffOverflow];
+  out->sweeps = D.aff_sweeps;
+  return GPC_OK;
+}
+
+int gpc_debug_affinity_table(gpc_ctx* ctx, uint32_t slot, gpc_affinity_entry* buf, size_t cap, size_t* n) {
+  if (!ctx || !n || (!buf && cap) || slot >= ctx->dev.size()) return -GPC_EINVAL;
+  *n = 0;
+  std::lock_guard<std::mutex> g(ctx->ctl);  // (the Service flows name the entries' destinations)
+  std::vector<uint32_t> w;
+  uint32_t now = 0;
+  {
+    std::lock_guard<std::mutex> d(ctx->data);
+    DevState& D = ctx->dev[slot];
+    if (!ctx->cfg.session_affinity || !D.d_aff) return GPC_OK;
+    now = aff_now(ctx);
+    w.resize(size_t(kAffSlotWords) << ctx->cfg.session_affinity);
+    if (hip_ok(hipSetDevice(D.device)) || hip_ok(hipDeviceSynchronize()) ||
+        hip_ok(hipMemcpy(w.data(), D.d_aff, w.size() * 4, hipMemcpyDeviceToHost)))
+      return -GPC_EDEV;
+  }
+  size_t k = 0;
+  for (size_t s = 0; s < w.size(); s += kAffSlotWords) {
+    const uint32_t* q = w.data() + s;
+    if (!(q[0] | q[1]) || now >= q[6]) continue;
+    if (k < cap) buf[k] = gpc_affinity_entry{q[1] >> 8, q[0], ctx->svc.affinity_dst(q[1] >> 8, q[1] & 0xffu), q[4], q[5], q[6]};
+    k++;
+  }
+  *n = k;
+  return k > cap ? -GPC_ERANGE : GPC_OK;
+}
+
 int gpc_classify(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, int32_t count, void* stream) {
   return gpc_classify_on(ctx, 0, pk, n, out, nullptr, count, stream);
 }
@@ -1250,21 +1409,45 @@ int gpc_classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n
   // streams never share one and the data path does no allocation once warm
   GroupArgs ga{nullptr, group_key(ctx), D.cur.base->axes, ctx->group_src_bits, ctx->group_xcd, ctx->group_unpermute,
                D.cur.svc && lb_out && ctx->group_unpermute};
-  // Service batches: 16 B per packet to park the fields the Service stage rewrites between the
+  // Session affinity: the bound Service image holds an affinity Service and the context has a table.
+  // The Service stage then runs in front (classify.hip aff_*_kernel) and the columns it rewrites
+  // lead the scratch, as the IPv6 Service stage's do; the policy batch has ct_dst, svc_group and dest
+  // columns whatever the caller gave. Any other batch takes exactly the launches it took before.
+  const bool affinity = n && D.cur.svc && D.cur.svc->affinity && ctx->cfg.session_affinity;
+  // Other Service batches: 16 B per packet to park the fields the Service stage rewrites between the
   // egress and the ingress launch (classify.hip launch); without it (no memory) one launch does both
-  const size_t park_bytes = D.cur.svc && n && ctx->svc_split ? (16 * n + 255) & ~size_t(255) : 0;
+  const size_t park_bytes = affinity ? (size_t(aff_lb_scratch_bytes(n)) + 255) & ~size_t(255)
+                            : D.cur.svc && n && ctx->svc_split ? (16 * n + 255) & ~size_t(255) : 0;
+  gpc_pkt_soa shape = *pk;  // which columns the policy batch has (group_scratch_bytes reads presence only)
+  if (affinity) {
+    shape.ct_dst = shape.svc_group = pk->src;
+    shape.dest = reinterpret_cast<const uint8_t*>(pk->src);
+    ga.lb = 0;  // the LB results are stored at caller indexes by aff_resolve_kernel
+  }
   uint8_t* scratch = nullptr;
   if (group_batch(ctx, n, *D.cur.base, jpool && D.cur.jmode == kModeJournal)) {
-    if (const int e = group_scratch_for(ctx, D, st, park_bytes + group_scratch_bytes(*pk, n, ga.lb), &scratch)) return e;
+    if (const int e = group_scratch_for(ctx, D, st, park_bytes + group_scratch_bytes(shape, n, ga.lb), &scratch)) return e;
     if (scratch) ga.scratch = scratch + park_bytes;
   }
+  if (affinity && !scratch)
+    if (const int e = group_scratch(D, st, park_bytes, &scratch)) return e;
   if (park_bytes && !scratch && group_scratch(D, st, park_bytes, &scratch)) {
     (void)hipGetLastError();
     scratch = nullptr;  // a performance choice, never a data-path failure
   }
-  int rc = launch_classify(ep, *pk, n, out, reinterpret_cast<uint4*>(lb_out), D.d_counters, count,
-                           ga.scratch ? &ga : nullptr, st, n ? next_marks(D) : nullptr,
-                           park_bytes && scratch ? reinterpret_cast<uint4*>(scratch) : nullptr);
+  int rc;
+  if (affinity) {
+    AffLaunch al;
+    LaunchMarks* marks = next_marks(D);
+    if ((rc = aff_prepare(ctx, D, st, marks, &al))) return rc;
+    al.lb_scratch = scratch;
+    rc = launch_classify_aff(ep, *pk, n, out, reinterpret_cast<uint4*>(lb_out), D.d_counters, count,
+                             ga.scratch ? &ga : nullptr, st, marks, al);
+  } else {
+    rc = launch_classify(ep, *pk, n, out, reinterpret_cast<uint4*>(lb_out), D.d_counters, count,
+                         ga.scratch ? &ga : nullptr, st, n ? next_marks(D) : nullptr,
+                         park_bytes && scratch ? reinterpret_cast<uint4*>(scratch) : nullptr);
+  }
   if (!rc && scratch) rc = group_scratch_used(D, st);
   if (rc || n == 0) return rc;
   pace.record();
@@ -1314,8 +1497,34 @@ int gpc_trace(gpc_ctx* ctx, const gpc_pkt_soa* pk, gpc_verdict* out, gpc_lb_resu
     } else {
       EpochArgs ep{cur.base->d_hdr, cur.base->d_blob, cur.jhdr ? cur.pool->d_blob : nullptr, cur.jhdr,
                    cur.svc ? cur.svc->d_blob : nullptr, 0u, {0, 0}, 0u, 0u};
-      rc = launch_trace(ep, d, dout, dlb, dsteps, dn, nullptr);
+      DevState& D = ctx->dev[0];
+      uint8_t* ascr = nullptr;
+      bool noep = false;
+      // Session affinity with a table in use: the Service stage runs read-only over the table
+      // (aff_resolve_kernel: a live entry gives the learned Endpoint, nothing is learned) and the
+      // walk is traced over the columns it rewrote, as a batch's policy launches read them.
+      if (cur.svc && cur.svc->affinity && ctx->cfg.session_affinity && D.d_aff) {
+        gpc_pkt_soa rw{};
+        AffLaunch al{aff_table(ctx, D), aff_now(ctx), 0u, 1u, nullptr, nullptr};
+        uint8_t dest0 = 0;
+        if (hip_ok(hipMalloc((void**)&ascr, aff_lb_scratch_bytes(1))) || hip_ok(hipStreamWaitEvent(nullptr, D.aff_done, 0))) rc = -GPC_EDEV;
+        al.lb_scratch = ascr;
+        if (!rc) rc = launch_classify_aff(ep, d, 1, nullptr, dlb, nullptr, 0, nullptr, nullptr, nullptr, al, &rw);
+        if (!rc) rc = hip_ok(hipMemcpy(&dest0, rw.dest, 1, hipMemcpyDeviceToHost));
+        noep = (dest0 & kDestNoEndpoint) != 0;
+        d = rw;
+        ep.svc = nullptr;
+        if (!rc && noep) {  // rejected in EndpointDNAT before any rule table
+          const uint32_t v[4] = {0u, pack_verdict(GPC_ACT_REJECT, GPC_VTABLE_ENDPOINT_DNAT, 0, 0), 0u, 0u};
+          const uint32_t zero = 0;
+          if (hip_ok(hipMemcpy(dout, v, 16, hipMemcpyHostToDevice)) || hip_ok(hipMemcpy(dn, &zero, 4, hipMemcpyHostToDevice)))
+            rc = -GPC_EDEV;
+        }
+      }
+      // (the traced walk zeroes the LB result of a batch without a Service image: kept apart here)
+      if (!rc && !noep) rc = launch_trace(ep, d, dout, ascr ? reinterpret_cast<uint4*>(buf + 32) : dlb, dsteps, dn, nullptr);
       if (!rc) rc = hip_ok(hipDeviceSynchronize());  // the epoch stays alive while it is current
+      if (ascr) (void)hipFree(ascr);
     }
   }
   if (!rc) rc = hip_ok(hipMemcpy(h.data(), buf, kOut, hipMemcpyDeviceToHost));
@@ -1659,7 +1868,8 @@ int gpc_set_launch_timing(gpc_ctx* ctx, uint32_t slots) {
 int gpc_launch_times(gpc_ctx* ctx, gpc_launch_time* out, size_t cap, size_t* n) {
   if (!ctx || !n || (!out && cap)) return -GPC_EINVAL;
   static const char* const names[kLaunchKinds] = {"group_tiles", "classify_egress", "classify_ingress", "classify_both",
-                                                  "unpermute",   "v6_codes",        "v6_lb"};
+                                                  "unpermute",   "v6_codes",        "v6_lb",            "aff_learn",
+                                                  "aff_resolve", "aff_sweep"};
   double ms[kLaunchKinds] = {};
   uint32_t cnt[kLaunchKinds] = {};
   size_t dropped = 0;
@@ -2083,6 +2293,7 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
     }
     if (!svc_changed) ne[k].svc = D.cur.svc, ne[k].svc6 = D.cur.svc6;
     else if (!ctx->svc_blob.empty() && (rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc))) return fail(rc);
+    if (svc_changed && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
     if (svc_changed && !ctx->svc6_blob.empty() && (rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6))) return fail(rc);
     ne[k].epoch = epoch;
     // counters: grow to the slot count, zero released slots (their Metric flows were deleted)

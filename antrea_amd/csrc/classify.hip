@@ -1026,6 +1026,146 @@ int launch_classify(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_
   return hipGetLastError() == hipSuccess ? 0 : -GPC_EDEV;
 }
 
+// Session affinity of IPv4 Services (core.hpp "Affinity table"): the Service stage of a batch against
+// an image with affinity Services runs in front of the policy launches, as v6_lb_kernel does for
+// IPv6 -- aff_sweep_kernel (when the clock moved), aff_learn_kernel, aff_resolve_kernel -- and the
+// policy launches then run as `resolved` over the columns aff_resolve_kernel wrote. One packet (one
+// slot in the sweep) per lane, 256-thread blocks, the tail bounds-checked; no lane waits for another.
+struct AffOpsDev {
+  static __device__ __forceinline__ uint64_t cas(uint64_t* p, uint64_t expect, uint64_t v) {
+    return atomicCAS(reinterpret_cast<unsigned long long*>(p), (unsigned long long)expect, (unsigned long long)v);
+  }
+  static __device__ __forceinline__ void min(uint64_t* p, uint64_t v) {
+    atomicMin(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
+  }
+  // one atomic per wavefront for the lanes whose `pred` holds
+  static __device__ __forceinline__ void count(unsigned long long* c, bool pred) {
+    const unsigned long long m = __ballot(pred);
+    if (pred && (__lane_id() == unsigned(__ffsll((long long)m) - 1))) atomicAdd(c, (unsigned long long)__popcll(m));
+  }
+};
+struct AffArgs {
+  const uint32_t* svc;  // IPv4 Service image with affinity Services
+  AffTable tab;
+  uint32_t now, seq, read_only;
+  const uint32_t *src, *dst;
+  const uint16_t *sport, *dport;
+  const uint8_t* proto;
+  const uint32_t *out_port, *svc_group;  // svc_group, dest, ct_state: optional
+  const uint8_t *dest, *ct_state;
+  uint32_t* dst_out;
+  uint16_t* dport_out;
+  uint32_t *out_port_out, *svc_group_out;
+  uint8_t* dest_out;
+  uint4* lb_out;  // may be null
+};
+// The counters are striped over kAffCounterStripes copies (a block adds to copy blockIdx mod that): one
+// copy would take an atomic from nearly every wavefront of a batch, all on one address.
+__device__ __forceinline__ AffTable aff_striped(AffTable t) {
+  t.ctr += (blockIdx.x % kAffCounterStripes) * kAffCounters;
+  return t;
+}
+__global__ __launch_bounds__(kLbBlock) void aff_sweep_kernel(AffTable t, uint32_t now, uint32_t mode) {
+  t = aff_striped(t);
+  const uint64_t s = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
+  if (s < (uint64_t(1) << t.log2)) aff_sweep_slot<AffOpsDev>(t, uint32_t(s), now, mode);
+}
+__global__ __launch_bounds__(kLbBlock) void aff_learn_kernel(AffArgs a, uint64_t n) {
+  const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
+  if (i >= n) return;
+  a.tab = aff_striped(a.tab);
+  aff_learn<AffOpsDev>(a.svc, a.tab, a.now, a.seq, uint32_t(i), a.src[i], a.dst[i], a.dport[i], a.proto[i],
+                       a.ct_state ? a.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK));
+}
+__global__ __launch_bounds__(kLbBlock) void aff_resolve_kernel(AffArgs a, uint64_t n) {
+  const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
+  if (i >= n) return;
+  a.tab = aff_striped(a.tab);
+  uint32_t dst = a.dst[i], dport = a.dport[i];
+  uint32_t out_port = a.out_port[i];
+  uint32_t svc_group = a.svc_group ? a.svc_group[i] : 0u;
+  uint32_t dest = a.dest ? a.dest[i] : 0u;
+  uint32_t lb[4];
+  const uint32_t f = lb_stage_aff(a.svc, a.tab, a.now, a.seq, a.read_only != 0u, uint32_t(i), a.src[i], dst, a.sport[i], a.sport,
+                                  dport, a.proto[i], svc_group, out_port, dest, lb);
+  if (!a.read_only) {
+    AffOpsDev::count(a.tab.ctr + kAffLearned, (f & GPC_LB_LEARNED) != 0u);
+    AffOpsDev::count(a.tab.ctr + kAffHits, (f & (GPC_LB_AFFINITY | GPC_LB_LEARNED)) == GPC_LB_AFFINITY);
+  }
+  a.dst_out[i] = dst;
+  a.dport_out[i] = uint16_t(dport);
+  a.out_port_out[i] = out_port;
+  a.svc_group_out[i] = svc_group;
+  a.dest_out[i] = uint8_t((dest & ~kDestNoEndpoint) | ((f & GPC_LB_NO_ENDPOINT) ? kDestNoEndpoint : 0u));
+  if (a.lb_out) a.lb_out[i] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
+}
+
+uint64_t aff_lb_scratch_bytes(uint64_t n) {  // dst dport out_port svc_group dest, every region 256-B aligned
+  return (4 + 2 + 4 + 4 + 1) * n + 5 * 256;
+}
+
+int launch_aff_sweep(const AffTable& t, uint32_t now, uint32_t mode, hipStream_t stream, LaunchMarks* marks) {
+  launch_mark(marks, kLaunchAffSweep, stream);
+  const uint64_t slots = uint64_t(1) << t.log2;
+  hipLaunchKernelGGL(aff_sweep_kernel, dim3(uint32_t((slots + kLbBlock - 1) / kLbBlock)), dim3(kLbBlock), 0, stream, t, now, mode);
+  return hipGetLastError() == hipSuccess ? 0 : -GPC_EDEV;
+}
+
+int launch_classify_aff(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out, uint4* lb_out,
+                        unsigned long long* counters, int count, const GroupArgs* group, hipStream_t stream,
+                        LaunchMarks* marks, const AffLaunch& al, gpc_pkt_soa* rewritten) {
+  if (n == 0) return 0;
+  if (n > kMaxPackets || !ep.svc || !al.tab.w || !al.lb_scratch) return -GPC_EINVAL;
+  uint8_t* q = al.lb_scratch;
+  auto take = [&](uint64_t bytes) {
+    uint8_t* r = q;
+    q += (bytes + 255) & ~uint64_t(255);
+    return r;
+  };
+  AffArgs a{};
+  a.svc = ep.svc;
+  a.tab = al.tab;
+  a.now = al.now;
+  a.seq = al.seq;
+  a.read_only = al.read_only;
+  a.src = pk.src;
+  a.dst = pk.dst;
+  a.sport = pk.sport;
+  a.dport = pk.dport;
+  a.proto = pk.proto;
+  a.out_port = pk.out_port;
+  a.svc_group = pk.svc_group;
+  a.dest = pk.dest;
+  a.ct_state = pk.ct_state;
+  a.dst_out = reinterpret_cast<uint32_t*>(take(4 * n));
+  a.out_port_out = reinterpret_cast<uint32_t*>(take(4 * n));
+  a.svc_group_out = reinterpret_cast<uint32_t*>(take(4 * n));
+  a.dport_out = reinterpret_cast<uint16_t*>(take(2 * n));
+  a.dest_out = take(n);
+  a.lb_out = lb_out;
+  const dim3 grid(uint32_t((n + kLbBlock - 1) / kLbBlock));
+  if (!al.read_only) {
+    launch_mark(marks, kLaunchAffLearn, stream);
+    hipLaunchKernelGGL(aff_learn_kernel, grid, dim3(kLbBlock), 0, stream, a, n);
+  }
+  launch_mark(marks, kLaunchAffResolve, stream);
+  hipLaunchKernelGGL(aff_resolve_kernel, grid, dim3(kLbBlock), 0, stream, a, n);
+  // the table is free for the next affinity batch of the slot from here on
+  if (al.done && hipEventRecord(al.done, stream) != hipSuccess) return -GPC_EDEV;
+  gpc_pkt_soa p4 = pk;  // the policy launches read what the stage rewrote
+  p4.dst = a.dst_out;
+  p4.dport = a.dport_out;
+  p4.out_port = a.out_port_out;
+  p4.svc_group = a.svc_group_out;
+  p4.dest = a.dest_out;
+  if (!p4.ct_dst) p4.ct_dst = pk.dst;  // ct_nw_dst: the destination before the DNAT
+  if (rewritten) *rewritten = p4;
+  if (!out) return hipGetLastError() == hipSuccess ? 0 : -GPC_EDEV;  // (gpc_trace: the Service stage alone)
+  EpochArgs e = ep;
+  e.svc = nullptr;
+  return launch_classify(e, p4, n, out, nullptr, counters, count, group, stream, marks, nullptr, true);
+}
+
 #if defined(GPC_STAMPS)
 // Diagnostic builds: copy (and optionally clear) the region-stamp totals (tools/stamps.py).
 extern "C" int gpc_stamps_read(unsigned long long* out, int reset) {

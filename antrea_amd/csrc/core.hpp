@@ -2158,12 +2158,16 @@ struct SvcHdr {
   // Service exists): a packet to one of them that misses the (protocol, address, port) key takes
   // the NodePort key (protocol, 0, port) -- ServiceLB's ToNodePortAddressRegMark flows
   uint32_t np_off, n_np;
+  // Session affinity (0 / 0 without an affinity Service): n_svc install ids (0: the Service has no
+  // affinity), then n_np NodePort address ids, at aff_off
+  uint32_t aff_off, n_aff;
 };
 constexpr uint32_t kSvcMaxNodePortAddrs = 64;
 // Service hash: 2-choice cuckoo, buckets of two 16-B slots {key low, key high, service index, 0}:
 // a lookup is one 128-bit load per slot (four per packet), not a 96-B scan of an 8-way bucket.
 constexpr uint32_t kSvcBucketWords = 8, kSvcSlots = 2, kSvcSlotWords = 4;
 constexpr uint32_t kSvcLoadReg7 = 1u;  // service flag: the ServiceLB flow loads reg7 = group id
+constexpr uint32_t kSvcAffinity = 2u;  // ... loads EpToLearnRegMark: session affinity, hard timeout in flags >> 16
 // endpoint flags (port word >> 16): GPC_LB_DNAT / GPC_LB_REMOTE values
 GPC_HD uint64_t svc_key(uint32_t proto, uint32_t ip, uint32_t port) {
   return (1ull << 63) | (uint64_t(proto & 0xffu) << 48) | (uint64_t(port & 0xffffu) << 32) | ip;
@@ -2236,6 +2240,209 @@ GPC_HD uint32_t lb_stage(const uint32_t* sv, uint32_t src, uint32_t& dst, uint32
   const uint32_t slot = lb_hash(src, dst, sport, dport, proto) & ((1u << lg) - 1u);
   const uint32_t* e = sv + h->ep_off + 4 * (s[0] + slot % n);
   GPC_TOUCH(e, 16);
+  flags |= e[1] >> 16;
+  o[0] = e[0];
+  o[1] = (e[1] & 0xffffu) | (flags << 16);
+  o[3] = e[2];
+  if (flags & GPC_LB_DNAT) {
+    dst = e[0];
+    dport = e[1] & 0xffffu;
+  }
+  out_port = e[2];
+  dest = e[3];
+  return flags;
+}
+
+// ------------------------------------------------------------------------------ Affinity table
+// sessionAffinity: ClientIP of IPv4 Services: the learned flows of OVS's SessionAffinity table
+// (serviceLearnFlow, pipeline.go:2316-2371) as a mutable hash table of the device slot, updated by a
+// batch in parallel with the result of applying its packets in caller order.
+//   2^log2 slots of 32 B (two per 64-B line): a 64-bit key word, a 64-bit bid word, a 16-B entry
+//   {endpoint ip, port | (GPC_LB_REMOTE bit) << 16, expires, endpoint index hint}.
+//   key = (install id << 8 | NodePort address id) << 32 | client address: the install id (>= 1, one
+//   per gpc_install_service_flows of an affinity config) stands for protocol, port and Service IP,
+//   the address id (0: the Service IP) for the NodePort address the packet went to. Compared whole.
+//   0 = empty slot. A key has two candidate buckets of two slots (one line each), scanned in a fixed
+//   order; insertion never moves another key.
+//   bid word: the smallest (~launch_seq << 32 | caller index) bid on the slot. A newer launch always
+//   undercuts an older one, so the word is never reset between launches (all ones when never bid).
+// Three passes of a batch, each one kernel (classify.hip), written here over an `Ops` shim (device
+// atomics on the GPU, plain operations in the single-threaded host emulation):
+//   aff_sweep_slot   clears slots whose entry has expired (before the learn pass, never beside it);
+//   aff_learn        every +new packet to an affinity Service whose key has no live, still valid
+//                    entry finds or claims the key's slot and bids its caller index;
+//   lb_stage_aff     lb_stage for every packet; a packet of such a key takes the choice of the bid's
+//                    winner w when w <= its index (w itself writes the entry), its own otherwise;
+//                    without a bid of this launch a live valid entry gives the learned Endpoint.
+// Slots only go from empty to owned inside the learn pass, and ownership is decided from the value
+// the compare-and-swap returns, so every lane of a key converges on one slot.
+struct AffTable {
+  uint32_t* w;               // slots: 8 words each
+  uint32_t log2;             // 2^log2 slots, log2 >= 2
+  unsigned long long* ctr;   // kAffLearned .. (device: kAffCounterStripes copies)
+};
+constexpr uint32_t kAffSlotWords = 8;
+enum AffCounter : uint32_t { kAffLearned = 0, kAffHits = 1, kAffOverflow = 2, kAffLive = 3, kAffCounters = 4 };
+constexpr uint32_t kAffCounterStripes = 64;  // device: copies of the counter array, summed when read
+constexpr uint32_t kAffSweepExpired = 0, kAffSweepReset = 1, kAffSweepBids = 2, kAffSweepCount = 3;  // aff_sweep_slot modes
+constexpr uint32_t kAffNone = 0xffffffffu;
+
+GPC_HD uint64_t aff_key(uint32_t install, uint32_t np_id, uint32_t src) {
+  return (uint64_t((install << 8) | (np_id & 0xffu)) << 32) | src;
+}
+GPC_HD uint64_t* aff_key_word(const AffTable& t, uint32_t slot) { return reinterpret_cast<uint64_t*>(t.w + size_t(slot) * kAffSlotWords); }
+GPC_HD uint64_t* aff_bid_word(const AffTable& t, uint32_t slot) { return aff_key_word(t, slot) + 1; }
+GPC_HD uint32_t* aff_entry(const AffTable& t, uint32_t slot) { return t.w + size_t(slot) * kAffSlotWords + 4; }
+// The four candidate slots of a key, in scan order (the two buckets may coincide).
+GPC_HD void aff_candidates(uint64_t key, uint32_t log2, uint32_t* c) {
+  const uint32_t mask = (1u << (log2 - 1u)) - 1u;
+  const uint64_t k = key ^ 0x8ebc6af09c88c6e3ull;
+  const uint32_t b1 = hash_b1(k, mask), b2 = hash_b2(k, mask);
+  c[0] = 2u * b1, c[1] = 2u * b1 + 1u, c[2] = 2u * b2, c[3] = 2u * b2 + 1u;
+}
+// The slot that holds `key` (plain loads: a key claimed earlier in the running learn pass may not
+// show yet, which the claim below settles), or kAffNone.
+GPC_HD uint32_t aff_find(const AffTable& t, uint64_t key, const uint32_t* c) {
+  uint32_t r = kAffNone;
+#pragma unroll
+  for (int k = 3; k >= 0; k--) r = *aff_key_word(t, c[k]) == key ? c[k] : r;
+  return r;
+}
+// The Service a packet addresses, as lb_stage finds it: index into the service records or
+// kAffNone; np_id = id of the NodePort address it went to (0: the Service IP matched).
+GPC_HD uint32_t aff_svc_lookup(const uint32_t* sv, uint32_t proto, uint32_t dst, uint32_t dport, uint32_t& np_id) {
+  const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+  np_id = 0;
+  uint32_t si = svc_lookup(sv, proto, dst, dport);
+  if (si == 0xffffffffu && h->n_np) {
+    uint32_t at = kAffNone;
+    for (uint32_t i = 0; i < h->n_np; i++) at = sv[h->np_off + i] == dst ? i : at;
+    if (at != kAffNone) {
+      si = svc_lookup(sv, proto, 0u, dport);
+      if (h->n_aff) np_id = sv[h->aff_off + h->n_svc + at];
+    }
+  }
+  return si;
+}
+// Index (within the Service) of the Endpoint (ip, port) in the bound image, or kAffNone: a learned
+// Endpoint that has left the Service counts as a miss. `hint`: its index when it was learned.
+GPC_HD uint32_t aff_find_endpoint(const uint32_t* sv, const uint32_t* s, uint32_t ip, uint32_t port, uint32_t hint) {
+  const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+  const uint32_t n = s[1] & 0xffffffu;
+  const uint32_t* e = sv + h->ep_off + 4 * size_t(s[0]);
+  if (hint < n && e[4 * hint] == ip && (e[4 * hint + 1] & 0xffffu) == port) return hint;
+  for (uint32_t i = 0; i < n; i++)
+    if (e[4 * i] == ip && (e[4 * i + 1] & 0xffffu) == port) return i;
+  return kAffNone;
+}
+GPC_HD bool aff_entry_valid(const uint32_t* sv, const uint32_t* s, const uint32_t* e, uint32_t now, uint32_t* index) {
+  if (now >= e[2]) return false;  // hard timeout: live while now < expires
+  *index = aff_find_endpoint(sv, s, e[0], e[1] & 0xffffu, e[3]);
+  return *index != kAffNone;
+}
+
+// One slot of the sweep pass. kAffSweepExpired: an owned slot whose entry is dead becomes empty (its
+// bid word stays: bids of later launches undercut it). kAffSweepReset: everything (a new table).
+// kAffSweepBids: the bid words alone (the 32-bit launch sequence wrapped). kAffSweepCount: counts the
+// live entries into ctr[kAffLive], changes nothing.
+template <class Ops>
+GPC_HD void aff_sweep_slot(const AffTable& t, uint32_t slot, uint32_t now, uint32_t mode) {
+  uint64_t* const key = aff_key_word(t, slot);
+  uint32_t* const e = aff_entry(t, slot);
+  if (mode == kAffSweepCount) {
+    Ops::count(t.ctr + kAffLive, *key != 0 && now < e[2]);
+    return;
+  }
+  if (mode == kAffSweepReset || mode == kAffSweepBids) *aff_bid_word(t, slot) = ~0ull;
+  if (mode == kAffSweepReset || (mode == kAffSweepExpired && *key != 0 && now >= e[2])) {
+    *key = 0;
+    e[0] = e[1] = e[2] = e[3] = 0;
+  }
+}
+
+// The learn pass of packet i (caller index). Counts the packet in ctr[kAffOverflow] when its key
+// found no slot.
+template <class Ops>
+GPC_HD void aff_learn(const uint32_t* sv, const AffTable& t, uint32_t now, uint32_t seq, uint32_t i, uint32_t src, uint32_t dst,
+                      uint32_t dport, uint32_t proto, uint32_t ct_state) {
+  bool overflow = false;
+  if ((ct_state & GPC_CT_NEW) && (proto == 6 || proto == 17 || proto == 132)) {
+    const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+    uint32_t np_id;
+    const uint32_t si = aff_svc_lookup(sv, proto, dst, dport, np_id);
+    const uint32_t* s = sv + h->svc_off + 4 * size_t(si == kAffNone ? 0u : si);
+    if (si != kAffNone && (s[3] & kSvcAffinity) && (s[1] & 0xffffffu)) {
+      const uint64_t key = aff_key(sv[h->aff_off + si], np_id, src);
+      uint32_t c[4];
+      aff_candidates(key, t.log2, c);
+      uint32_t slot = aff_find(t, key, c), index;
+      const bool settled = slot != kAffNone && aff_entry_valid(sv, s, aff_entry(t, slot), now, &index);
+      if (!settled) {
+        for (int k = 0; k < 4 && slot == kAffNone; k++) {  // find or claim, in the fixed order
+          const uint64_t old = Ops::cas(aff_key_word(t, c[k]), 0ull, key);
+          if (old == 0ull || old == key) slot = c[k];
+        }
+        if (slot != kAffNone) Ops::min(aff_bid_word(t, slot), (uint64_t(~seq) << 32) | i);
+        overflow = slot == kAffNone;
+      }
+    }
+  }
+  Ops::count(t.ctr + kAffOverflow, overflow);
+}
+
+// lb_stage with the affinity branch (the resolve pass): `sport_col` is the batch's sport column at
+// caller indexes (the winner's choice is lb_hash with its sport: the rest of the hash input is the
+// key's). read_only (gpc_trace): the bid word is ignored and nothing is written. Returns the
+// GPC_LB_* flags, GPC_LB_AFFINITY / GPC_LB_LEARNED included.
+GPC_HD uint32_t lb_stage_aff(const uint32_t* sv, const AffTable& t, uint32_t now, uint32_t seq, bool read_only, uint32_t i,
+                             uint32_t src, uint32_t& dst, uint32_t sport, const uint16_t* sport_col, uint32_t& dport,
+                             uint32_t proto, uint32_t& svc_group, uint32_t& out_port, uint32_t& dest, uint32_t* o) {
+  o[0] = o[1] = o[2] = o[3] = 0;
+  if (proto != 6 && proto != 17 && proto != 132) return 0;
+  const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+  uint32_t np_id;
+  const uint32_t si = aff_svc_lookup(sv, proto, dst, dport, np_id);
+  if (si == kAffNone) return 0;
+  const uint32_t* s = sv + h->svc_off + 4 * size_t(si);
+  const uint32_t n = s[1] & 0xffffffu, lg = s[1] >> 24;
+  uint32_t flags = GPC_LB_HIT;
+  o[2] = s[2];
+  if (s[3] & kSvcLoadReg7) svc_group = s[2];
+  if (n == 0) {
+    flags |= GPC_LB_NO_ENDPOINT;
+    o[1] = flags << 16;
+    return flags;
+  }
+  uint32_t index = kAffNone, pick_sport = sport, slot = kAffNone;
+  if (s[3] & kSvcAffinity) {
+    const uint64_t key = aff_key(sv[h->aff_off + si], np_id, src);
+    uint32_t c[4];
+    aff_candidates(key, t.log2, c);
+    slot = aff_find(t, key, c);
+    if (slot != kAffNone) {
+      const uint64_t bid = *aff_bid_word(t, slot);
+      if (!read_only && uint32_t(bid >> 32) == ~seq) {  // a bid of this launch: winner = its low half
+        const uint32_t w = uint32_t(bid);
+        if (w <= i) {
+          pick_sport = sport_col[w];
+          flags |= GPC_LB_AFFINITY | (w == i ? uint32_t(GPC_LB_LEARNED) : 0u);
+        }
+      } else if (aff_entry_valid(sv, s, aff_entry(t, slot), now, &index)) {
+        flags |= GPC_LB_AFFINITY;
+      } else {
+        index = kAffNone;
+      }
+    }
+  }
+  if (index == kAffNone) index = (lb_hash(src, dst, pick_sport, dport, proto) & ((1u << lg) - 1u)) % n;
+  const uint32_t* e = sv + h->ep_off + 4 * (size_t(s[0]) + index);
+  if (flags & GPC_LB_LEARNED) {  // the winner: no other lane reads or writes this entry in this pass
+    uint32_t* w = aff_entry(t, slot);
+    w[0] = e[0];
+    w[1] = (e[1] & 0xffffu) | (((e[1] >> 16) & GPC_LB_REMOTE) << 16);
+    w[2] = now + (s[3] >> 16);
+    w[3] = index;
+  }
   flags |= e[1] >> 16;
   o[0] = e[0];
   o[1] = (e[1] & 0xffffu) | (flags << 16);

@@ -53,7 +53,8 @@ struct LaunchMarks {
   int n;
 };
 enum LaunchKind : uint8_t {
-  kLaunchGroup, kLaunchEgress, kLaunchIngress, kLaunchBoth, kLaunchUnpermute, kLaunchCodes, kLaunchV6Lb, kLaunchKinds, kLaunchEnd
+  kLaunchGroup, kLaunchEgress, kLaunchIngress, kLaunchBoth, kLaunchUnpermute, kLaunchCodes, kLaunchV6Lb, kLaunchAffLearn, kLaunchAffResolve,
+  kLaunchAffSweep, kLaunchKinds, kLaunchEnd
 };
 inline void launch_mark(LaunchMarks* m, uint8_t kind, hipStream_t s) {
   if (!m || m->n >= LaunchMarks::kMax) return;
@@ -79,4 +80,26 @@ int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc
                      unsigned long long* counters, int count, const GroupArgs* group, uint32_t* codes, hipStream_t stream,
                      LaunchMarks* marks = nullptr, const uint32_t* svc6 = nullptr, uint8_t* lb_scratch = nullptr,
                      uint4* lb_out6 = nullptr);
+// IPv4 batch against a Service image with session-affinity Services (ep.svc) and the slot's affinity
+// table (core.hpp "Affinity table"): aff_learn_kernel and aff_resolve_kernel run the Service stage
+// with the learned flows and write the columns it rewrites into lb_scratch
+// (aff_lb_scratch_bytes(n) bytes) and the optional LB results to lb_out; `done` is recorded after
+// them (the next affinity batch of the slot waits for it); the policy launches then run as
+// `resolved` over those columns with ct_dst = the caller's column or the original dst (`group`:
+// sized for a batch that has ct_dst, svc_group and dest columns). out == null: the stage alone;
+// *rewritten (optional) = the batch as the policy launches read it.
+// read_only (gpc_trace): no learn pass, the table is only read.
+struct AffLaunch {
+  AffTable tab;
+  uint32_t now, seq, read_only;
+  uint8_t* lb_scratch;
+  hipEvent_t done;
+};
+uint64_t aff_lb_scratch_bytes(uint64_t n);
+// One pass over the table's slots (core.hpp aff_sweep_slot modes), in front of a learn pass on the
+// same stream or on its own.
+int launch_aff_sweep(const AffTable& t, uint32_t now, uint32_t mode, hipStream_t stream, LaunchMarks* marks = nullptr);
+int launch_classify_aff(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out, uint4* lb_out,
+                        unsigned long long* counters, int count, const GroupArgs* group, hipStream_t stream,
+                        LaunchMarks* marks, const AffLaunch& al, gpc_pkt_soa* rewritten = nullptr);
 }

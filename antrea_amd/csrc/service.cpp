@@ -19,6 +19,8 @@ constexpr uint32_t kSvcNoEp = 1u << 14;            // reg0[14]  SvcNoEpRegMark
 constexpr uint32_t kEpStateMask = 0x7u << 16;      // reg4[16..18] ServiceEPStateField
 constexpr uint32_t kEpToSelect = 0x1u << 16;
 constexpr uint32_t kEpSelected = 0x2u << 16;
+constexpr uint32_t kEpToLearn = 0x3u << 16;        // EpToLearnRegMark (session affinity)
+constexpr uint32_t kMaxInstallId = (1u << 24) - 1, kMaxNodePortId = 255;  // core.hpp aff_key
 constexpr uint32_t kToNodePort = 1u << 19;         // reg4[19]  ToNodePortAddressRegMark
 constexpr uint32_t kToExternal = 1u << 21;         // reg4[21]  ToExternalAddressRegMark
 constexpr uint32_t kVirtualNodePortDNAT = 0xa9fe00fcu;  // config.VirtualNodePortDNATIPv4 169.254.0.252
@@ -221,8 +223,11 @@ static std::string service_key(const IPAddr& ip, uint16_t port, uint8_t proto) {
 // InstallServiceFlows (client.go:790-807) -> serviceLBFlows (pipeline.go:2373-2431).
 int FeatureService::install_service_flows(const gpc_service_config& c) {
   if (!ip_proto(c.protocol) || !family_ok(c.family)) return -GPC_EINVAL;
-  if (c.affinity_timeout || c.is_dsr || c.is_nested || (c.is_external && c.traffic_policy_local))
-    return -GPC_EINVAL;  // learn / DSR / multi-cluster / short-circuit flows: not modelled
+  if (c.is_dsr || c.is_nested || (c.is_external && c.traffic_policy_local))
+    return -GPC_EINVAL;  // DSR / multi-cluster / short-circuit flows: not modelled
+  // learn flows: IPv4 Services of a context with an affinity table
+  if (c.affinity_timeout && (!cfg_.session_affinity || c.family != 4)) return -GPC_EINVAL;
+  if (c.affinity_timeout && next_install_ >= kMaxInstallId) return -GPC_ENOMEM;
   const IPAddr ip = to_ip(c.ip, c.family);
   const uint32_t gid = c.traffic_policy_local ? c.local_group_id : c.cluster_group_id;  // TrafficPolicyGroupID
   Flow f;
@@ -241,13 +246,41 @@ int FeatureService::install_service_flows(const gpc_service_config& c) {
     f.m.nw_dst.addr = ip;
   }
   f.acts.push_back(set_reg(0, kRewriteMac, kRewriteMac));
-  f.acts.push_back(set_reg(4, kEpSelected, kEpStateMask));
+  f.acts.push_back(set_reg(4, c.affinity_timeout ? kEpToLearn : kEpSelected, kEpStateMask));
   if (c.is_external) f.acts.push_back(set_reg(4, kToExternal, kToExternal));
   if (cfg_.enable_antrea_policy) f.acts.push_back(set_reg(7, gid));
   Action g{ACT_GROUP};
   g.a = gid;
   f.acts.push_back(g);
-  cached_[service_key(ip, c.port, c.protocol)] = {f};
+  std::vector<Flow> flows = {f};
+  if (c.affinity_timeout) {  // serviceLearnFlow (pipeline.go:2316-2371)
+    Flow l;
+    l.table = TB_SERVICE_LB;
+    l.priority = kPriorityLow;
+    l.cookie = cookie() | gid;  // RequestWithObjectID(category, TrafficPolicyGroupID)
+    set_proto(l.m, ip_proto(c.protocol), c.family);
+    l.m.has_tp_dst = true;
+    l.m.tp_dst = c.port;
+    l.m.tp_dst_m = 0xffff;
+    match_reg(l.m, 4, kEpToLearn, kEpStateMask);
+    if (c.is_nodeport) {
+      match_reg(l.m, 4, kToNodePort, kToNodePort);
+    } else {
+      l.m.nw_dst.set = true;
+      l.m.nw_dst.addr = ip;
+    }
+    Action learn{ACT_LEARN};
+    learn.a = c.affinity_timeout;
+    learn.b = ip_proto(c.protocol);
+    learn.c = c.is_external;
+    learn.lv = l.cookie;
+    learn.lm = ++next_install_;  // the install id of its learned flows
+    Action nx{ACT_GOTO};
+    nx.a = TB_ENDPOINT_DNAT;
+    l.acts = {learn, set_reg(4, kEpSelected, kEpStateMask), nx};
+    flows.push_back(l);
+  }
+  cached_[service_key(ip, c.port, c.protocol)] = flows;
   generation_++;
   return GPC_OK;
 }
@@ -271,8 +304,6 @@ int FeatureService::set_node_port_addresses(const uint8_t* ips, uint8_t family, 
   if (!family_ok(family)) return -GPC_EINVAL;
   // cache keys: "NP" + address for IPv4, "N6" + address for IPv6 (one set per family)
   const char* const prefix = family == 6 ? "N6" : "NP";
-  for (auto it = cached_.begin(); it != cached_.end();)
-    it = it->first.compare(0, 2, prefix) == 0 ? cached_.erase(it) : std::next(it);
   std::vector<IPAddr> addrs;
   for (size_t i = 0; i < n; i++) {
     const IPAddr a = to_ip(ips + 16 * i, family);
@@ -289,6 +320,18 @@ int FeatureService::set_node_port_addresses(const uint8_t* ips, uint8_t family, 
     else for (int k = 0; k < 4; k++) v[k] = uint8_t(kVirtualNodePortDNAT >> (24 - 8 * k));
     addrs.push_back(to_ip(v, family));
   }
+  if (family == 4 && cfg_.session_affinity) {  // ids of the addresses, as the learned flows of NodePort Services key them
+    size_t fresh = 0;
+    for (const IPAddr& a : addrs) fresh += !np_ids_.count(a.v4());
+    if (np_ids_.size() + fresh > kMaxNodePortId) return -GPC_EINVAL;
+    for (const IPAddr& a : addrs)
+      if (!np_ids_.count(a.v4())) {
+        const uint32_t id = uint32_t(np_ids_.size()) + 1;
+        np_ids_[a.v4()] = id;
+      }
+  }
+  for (auto it = cached_.begin(); it != cached_.end();)
+    it = it->first.compare(0, 2, prefix) == 0 ? cached_.erase(it) : std::next(it);
   for (const IPAddr& a : addrs) {
     Flow f;
     f.table = TB_NODEPORT_MARK;
@@ -317,6 +360,17 @@ int FeatureService::uninstall_pod(const uint8_t* ip, uint8_t family) {
   else pods_.erase(to_ip(ip, 4).v4());
   generation_++;
   return GPC_OK;
+}
+
+uint32_t FeatureService::affinity_dst(uint32_t install, uint32_t np_id) const {
+  for (auto& kv : cached_)
+    for (auto& f : kv.second) {
+      if (f.acts.empty() || f.acts[0].kind != ACT_LEARN || f.acts[0].lm != install) continue;
+      if (f.m.nw_dst.set) return f.m.nw_dst.addr.v4();
+      for (auto& np : np_ids_)
+        if (np.second == np_id) return np.first;
+    }
+  return 0;
 }
 
 std::string FeatureService::dump_flows() const {
@@ -419,7 +473,12 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
     uint64_t key;
     uint32_t gid;
     bool reg7;
+    bool aff;  // the ServiceLB flow loads EpToLearnRegMark: its learn flow follows the group
   };
+  struct Learn {
+    uint32_t timeout, install;
+  };
+  std::map<uint64_t, Learn> learn;  // serviceLearnFlow per Service key
   std::vector<Svc> svcs;
   std::vector<uint32_t> node_port_addrs;
   bool any_node_port = false;
@@ -443,11 +502,23 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
         // a NodePort Service (ToNodePortAddressRegMark, no Service IP) is keyed by address 0
         const bool node_port = (f.m.reg_present & (1u << 4)) && (f.m.reg_m[4] & kToNodePort) && (f.m.reg_v[4] & kToNodePort);
         any_node_port |= node_port;
-        Svc s{svc_key(f.m.nw_proto, node_port ? 0u : f.m.nw_dst.addr.v4(), f.m.tp_dst), 0, false};
+        Svc s{svc_key(f.m.nw_proto, node_port ? 0u : f.m.nw_dst.addr.v4(), f.m.tp_dst), 0, false, false};
+        if (!f.acts.empty() && f.acts[0].kind == ACT_LEARN) {  // learn(...), EpSelected, goto EndpointDNAT
+          const Action& l = f.acts[0];
+          if ((f.m.reg_v[4] & kEpStateMask) != kEpToLearn || node_port == f.m.nw_dst.set || !f.m.has_tp_dst ||
+              f.m.tp_dst_m != 0xffff || !l.a || !l.lm || l.lm > kMaxInstallId || f.acts.back().kind != ACT_GOTO ||
+              f.acts.back().a != TB_ENDPOINT_DNAT) {
+            *err = "unsupported ServiceLB learn flow: " + f.str();
+            return -GPC_EINVAL;
+          }
+          learn[s.key] = Learn{l.a, uint32_t(l.lm)};
+          continue;
+        }
         bool grp = false;
         for (auto& a : f.acts) {
           if (a.kind == ACT_GROUP) s.gid = a.a, grp = true;
           if (a.kind == ACT_SET_REG && a.a == 7) s.reg7 = true;
+          if (a.kind == ACT_SET_REG && a.a == 4 && a.c == kEpStateMask) s.aff = a.b == kEpToLearn;
         }
         if (!grp || node_port == f.m.nw_dst.set || (f.m.nw_dst.set && f.m.nw_dst.plen >= 0) || !f.m.has_tp_dst ||
             f.m.tp_dst_m != 0xffff) {
@@ -457,9 +528,15 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
         svcs.push_back(s);
       }
     }
-  std::vector<uint32_t> svc_words, ep_words;
+  std::vector<uint32_t> svc_words, ep_words, aff_ids;
+  uint32_t n_aff = 0;
   std::vector<std::pair<uint64_t, uint32_t>> kv;
   for (auto& s : svcs) {
+    const auto lit = learn.find(s.key);
+    if (s.aff && lit == learn.end()) {
+      *err = "ServiceLB flow loads EpToLearnRegMark without a learn flow (group " + std::to_string(s.gid) + ")";
+      return -GPC_EINVAL;
+    }
     uint32_t first = uint32_t(ep_words.size() / 4), n = 0;
     auto git = groups_.find(s.gid);
     if (git != groups_.end() && group_is_v6(git->second)) {
@@ -469,16 +546,22 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
     if (git != groups_.end()) {
       for (auto& b : git->second.buckets) {
         uint32_t ip = 0, port = 0, flags = 0;
-        bool noep = false, to_dnat = false;
+        bool noep = false, to_dnat = false, to_lb = false;
         for (auto& a : b.acts) {
           if (a.kind == ACT_SET_REG && a.a == 3) ip = a.b;
           if (a.kind == ACT_SET_REG && a.a == 4 && a.c == 0xffffu) port = a.b;
           if (a.kind == ACT_SET_REG && a.a == 4 && (a.b & kRemoteEndpoint)) flags |= GPC_LB_REMOTE;
           if (a.kind == ACT_SET_REG && a.a == 0 && (a.b & kSvcNoEp)) noep = true;
-          if (a.kind == ACT_RESUBMIT) to_dnat = a.a == TB_ENDPOINT_DNAT;
+          if (a.kind == ACT_RESUBMIT) to_dnat = a.a == TB_ENDPOINT_DNAT, to_lb = a.a == TB_SERVICE_LB;
         }
-        if (!to_dnat) {
+        // a session-affinity bucket resubmits to ServiceLB, where the Service's learn flow takes the
+        // packet on to EndpointDNAT: bucket -> learn flow -> EndpointDNAT
+        if (!(to_dnat || (to_lb && s.aff)) || (to_lb && noep)) {
           *err = "unsupported group bucket (session affinity): " + git->second.str();
+          return -GPC_EINVAL;
+        }
+        if (s.aff && to_dnat && !noep) {
+          *err = "session-affinity Service whose group bypasses its learn flow: " + git->second.str();
           return -GPC_EINVAL;
         }
         if (noep) continue;
@@ -503,7 +586,10 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
       return -GPC_EINVAL;
     }
     kv.push_back({s.key, uint32_t(svc_words.size() / 4)});
-    svc_words.insert(svc_words.end(), {first, n | (lg << 24), s.gid, s.reg7 ? kSvcLoadReg7 : 0u});
+    svc_words.insert(svc_words.end(), {first, n | (lg << 24), s.gid,
+                                       (s.reg7 ? kSvcLoadReg7 : 0u) | (s.aff ? kSvcAffinity | (lit->second.timeout << 16) : 0u)});
+    aff_ids.push_back(s.aff ? lit->second.install : 0u);
+    n_aff += s.aff;
   }
   SvcHash h;
   if (!h.build(kv)) {
@@ -529,8 +615,19 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
   }
   hdr.np_off = hdr.ep_off + uint32_t(ep_words.size());
   hdr.n_np = uint32_t(node_port_addrs.size());
-  blob->assign(hdr.np_off + node_port_addrs.size(), 0u);
+  // session affinity: the install id of every Service (0: none) and the id of every NodePort
+  // address, after the rest -- an image without an affinity Service has neither
+  hdr.n_aff = n_aff;
+  hdr.aff_off = n_aff ? hdr.np_off + hdr.n_np : 0u;
+  blob->assign(hdr.np_off + node_port_addrs.size() + (n_aff ? aff_ids.size() + node_port_addrs.size() : 0), 0u);
   std::copy(node_port_addrs.begin(), node_port_addrs.end(), blob->begin() + hdr.np_off);
+  if (n_aff) {
+    std::copy(aff_ids.begin(), aff_ids.end(), blob->begin() + hdr.aff_off);
+    for (size_t i = 0; i < node_port_addrs.size(); i++) {
+      const auto it = np_ids_.find(node_port_addrs[i]);
+      (*blob)[hdr.aff_off + aff_ids.size() + i] = it == np_ids_.end() ? 0u : it->second;
+    }
+  }
   std::memcpy(blob->data(), &hdr, sizeof hdr);
   for (auto& e : kv) {
     const uint32_t mb = svc_map_bit(e.first, hdr.map_log2);

@@ -33,6 +33,9 @@ class FeatureService {
   std::string dump_flows() const;   // FlowModToString lines of the realized Service flows
   std::string dump_groups() const;  // Group::str lines
   bool empty() const { return cached_.empty() && groups_.empty(); }
+  // Session affinity (gpc_config.session_affinity): the destination a learned flow of install id
+  // `install` and NodePort address id `np_id` matches (NXM_OF_IP_DST); 0 when no longer realized.
+  uint32_t affinity_dst(uint32_t install, uint32_t np_id) const;
   uint64_t generation() const { return generation_; }
 
   // Device Service image (core.hpp "Service image"), IPv4. Returns -GPC_EINVAL with *err for a
@@ -56,6 +59,11 @@ class FeatureService {
   bool family_ok(uint8_t family) const { return family == 4 || (family == 6 && cfg_.ipv6_enabled); }
   bool has_state(uint8_t family) const;              // some flow or group of that family is realized
   uint64_t generation_ = 0;
+  // Session affinity. Install ids: one per install_service_flows of an affinity config, carried by
+  // its learn flow (Action::lm), 24 bits, never reused. NodePort address ids: one per IPv4 NodePort
+  // address ever set, 8 bits, never reused (the learned flows' NXM_OF_IP_DST of a NodePort Service).
+  uint32_t next_install_ = 0;
+  std::map<uint32_t, uint32_t> np_ids_;
 };
 
 }  // namespace gpc

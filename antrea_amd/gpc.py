@@ -40,6 +40,10 @@ LB_DTYPE = np.dtype([("endpoint_ip", "<u4"), ("endpoint_port", "<u2"), ("flags",
 LB6_DTYPE = np.dtype([("endpoint_ip", "u1", (16,)), ("endpoint_port", "<u2"), ("flags", "u1"), ("reserved", "u1"),
                       ("group_id", "<u4"), ("out_port", "<u4"), ("reserved2", "<u4")])
 LB_HIT, LB_NO_ENDPOINT, LB_DNAT, LB_REMOTE = 1, 2, 4, 8
+LB_AFFINITY, LB_LEARNED = 0x10, 0x20  # session affinity: Endpoint from a learned entry / this packet created it
+# gpc_affinity_entry (gpc_debug_affinity_table)
+AFF_ENTRY_DTYPE = np.dtype([("install_id", "<u4"), ("src", "<u4"), ("dst", "<u4"), ("endpoint_ip", "<u4"),
+                            ("endpoint_port", "<u4"), ("expires", "<u4")])
 VFLAG_PASS, VFLAG_TIE, VFLAG_PACKETIN = 1, 2, 4  # gpc_verdict.flags
 VTABLE_ENDPOINT_DNAT = 4
 
@@ -49,7 +53,7 @@ class gpc_config(C.Structure):
                 ("enable_deny_tracking", C.c_int32), ("cookie", C.c_uint64), ("device", C.c_int32),
                 ("compact_after", C.c_int32), ("ovs_meters", C.c_int32), ("external_node", C.c_int32),
                 ("group_packets", C.c_int32), ("group_key", C.c_int32), ("launch_pacing", C.c_int32),
-                ("reserved", C.c_int32 * 1)]
+                ("session_affinity", C.c_int32)]
 
 
 class gpc_addr(C.Structure):
@@ -112,6 +116,10 @@ class gpc_image_stats(C.Structure):
                 ("n_ext_values", C.c_uint32), ("n_pool_collections", C.c_uint64)]
 
 
+class gpc_affinity_counts(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("slots", "live", "learned", "hits", "overflow", "sweeps")]
+
+
 class gpc_endpoint(C.Structure):
     _fields_ = [("family", C.c_uint8), ("is_local", C.c_uint8), ("has_node_name", C.c_uint8), ("is_node_ip", C.c_uint8),
                 ("port", C.c_uint16), ("reserved", C.c_uint16), ("ip", C.c_uint8 * 16)]
@@ -135,7 +143,8 @@ EXPORTS = ["gpc_create", "gpc_destroy", "gpc_initialize", "gpc_install_rule", "g
            "gpc_add_dns_conj_addrs", "gpc_del_dns_conj_addrs", "gpc_network_policy_flow_keys", "gpc_stream_epoch", "gpc_trace", "gpc_replay",
            "gpc_set_launch_timing", "gpc_launch_times", "gpc_create_multi", "gpc_n_devices", "gpc_classify_on",
            "gpc_classify6_on", "gpc_classify_host_on", "gpc_counters_on", "gpc_debug_epoch6", "gpc_debug_fail_uploads",
-           "gpc_classify6_lb", "gpc_classify6_lb_on", "gpc_classify6_host_lb", "gpc_debug_service_image6"]
+           "gpc_classify6_lb", "gpc_classify6_lb_on", "gpc_classify6_host_lb", "gpc_debug_service_image6",
+           "gpc_set_affinity_clock", "gpc_affinity_stats", "gpc_debug_affinity_table"]
 
 _lib = None
 
@@ -211,6 +220,9 @@ def load(path: str = LIB_PATH):
     lib.gpc_trace.argtypes = [vp, C.POINTER(gpc_pkt_soa), vp, vp, C.POINTER(gpc_trace_step), sz, C.POINTER(sz)]
     lib.gpc_set_launch_timing.argtypes = [vp, C.c_uint32]
     lib.gpc_launch_times.argtypes = [vp, C.POINTER(gpc_launch_time), sz, C.POINTER(sz)]
+    lib.gpc_set_affinity_clock.argtypes = [vp, C.c_uint32]
+    lib.gpc_affinity_stats.argtypes = [vp, C.c_uint32, C.POINTER(gpc_affinity_counts)]
+    lib.gpc_debug_affinity_table.argtypes = [vp, C.c_uint32, vp, sz, C.POINTER(sz)]
     lib.gpc_strerror.argtypes = [i32]
     lib.gpc_strerror.restype = C.c_char_p
     _lib = lib
@@ -401,14 +413,15 @@ class Classifier:
 
     def __init__(self, ipv4=True, ipv6=False, enable_antrea_policy=True, enable_deny_tracking=False,
                  cookie=0x1020000000000, device=0, compact_after=0, ovs_meters=False, k8s_node=True, group_packets=0,
-                 group_key=0, devices=None, launch_pacing=0):
+                 group_key=0, devices=None, launch_pacing=0, session_affinity=0):
         self.lib = load()
         cfg = gpc_config(ipv4_enabled=int(ipv4), ipv6_enabled=int(ipv6),
                          enable_antrea_policy=int(enable_antrea_policy),
                          enable_deny_tracking=int(enable_deny_tracking), cookie=cookie, device=device,
                          compact_after=int(compact_after), ovs_meters=int(ovs_meters),
                          external_node=int(not k8s_node), group_packets=int(group_packets),
-                         group_key=int(group_key), launch_pacing=int(launch_pacing))
+                         group_key=int(group_key), launch_pacing=int(launch_pacing),
+                         session_affinity=int(session_affinity))
         h = C.c_void_p()
         if devices is None:
             _check(self.lib.gpc_create(C.byref(cfg), C.byref(h)), "gpc_create")
@@ -600,6 +613,28 @@ class Classifier:
             C.memmove(C.byref(buf, 16 * i), b, 16)
         _check(self.lib.gpc_set_node_port_addresses(self.h, buf, family, len(ips)), "gpc_set_node_port_addresses")
 
+    # --- session affinity (gpc_config.session_affinity)
+    def set_affinity_clock(self, seconds: int):
+        """The clock (seconds, monotonic) the learned entries' hard timeouts are measured on."""
+        _check(self.lib.gpc_set_affinity_clock(self.h, int(seconds)), "gpc_set_affinity_clock")
+
+    def affinity_stats(self, slot=0) -> dict:
+        st = gpc_affinity_counts()
+        _check(self.lib.gpc_affinity_stats(self.h, int(slot), C.byref(st)), "gpc_affinity_stats")
+        return {k: getattr(st, k) for k in ("slots", "live", "learned", "hits", "overflow", "sweeps")}
+
+    def affinity_table(self, slot=0) -> np.ndarray:
+        """Host copy of the live learned entries of a slot (AFF_ENTRY_DTYPE)."""
+        n = C.c_size_t()
+        rc = self.lib.gpc_debug_affinity_table(self.h, int(slot), None, 0, C.byref(n))
+        if rc not in (0, -GPC_ERANGE):
+            _check(rc, "gpc_debug_affinity_table")
+        buf = np.zeros(n.value, dtype=AFF_ENTRY_DTYPE)
+        if n.value:
+            _check(self.lib.gpc_debug_affinity_table(self.h, int(slot), buf.ctypes.data, n.value, C.byref(n)),
+                   "gpc_debug_affinity_table")
+        return buf
+
     def dump_groups(self) -> List[str]:
         need = C.c_size_t()
         self.lib.gpc_dump_groups(self.h, None, 0, C.byref(need))
@@ -698,9 +733,9 @@ class Classifier:
 
     def launch_times(self) -> Dict[str, dict]:
         """gpc_launch_times: {kernel: {"launches", "total_ms", "mean_ms", "dropped"}} since the last call."""
-        arr = (gpc_launch_time * 8)()
+        arr = (gpc_launch_time * 16)()
         n = C.c_size_t()
-        _check(self.lib.gpc_launch_times(self.h, arr, 8, C.byref(n)), "gpc_launch_times")
+        _check(self.lib.gpc_launch_times(self.h, arr, 16, C.byref(n)), "gpc_launch_times")
         return {arr[i].kernel.decode(): {"launches": arr[i].launches, "total_ms": arr[i].total_ms,
                                          "mean_ms": arr[i].total_ms / max(1, arr[i].launches),
                                          "dropped": arr[i].dropped} for i in range(n.value)}

@@ -248,14 +248,18 @@ VIRTUAL_NODE_PORT_DNAT = "169.254.0.252"                    # config.VirtualNode
 
 
 def add_services(wl: Workload, n_services: int, eps_per_service: int, seed=RULE_SEED + 4, remote_frac=0.7,
-                 noep_frac=0.02, local_policy_frac=0.1, svc_frac=0.5, nodeport_frac=0.0) -> Workload:
+                 noep_frac=0.02, local_policy_frac=0.1, svc_frac=0.5, nodeport_frac=0.0, affinity_frac=0.0,
+                 affinity_timeout=100) -> Workload:
     """ClusterIP Services (10.96.0.0/12) with `eps_per_service` Endpoints each: local Endpoints are
     the workload's local Pods (ofports known to the Pod map), remote ones are Pods on other Nodes
     (10.128.0.0/9). A fraction of Services has no Endpoints, a fraction Local traffic policy.
     `svc_frac` of the generated packets are aimed at a Service (ip, port, protocol).
     `nodeport_frac` > 0: that fraction are NodePort Services (installed with the virtual NodePort
     DNAT IP, as the proxier does, on ports 30000-32767 unique per protocol); their packets go to one
-    of NODE_PORT_ADDRESSES or the virtual IP; wl.node_port_addresses is set."""
+    of NODE_PORT_ADDRESSES or the virtual IP; wl.node_port_addresses is set.
+    `affinity_frac` > 0: that fraction of the Services has sessionAffinity: ClientIP with
+    `affinity_timeout` seconds (their configs carry affinity_timeout, their groups are installed with
+    session affinity: wl.affinity_groups); needs a Classifier(session_affinity=...)."""
     rng = np.random.default_rng(seed)
     base = int(ipaddress.ip_address("10.96.0.0"))
     ips = base + 1 + rng.choice(1 << 20, size=n_services, replace=False)
@@ -300,6 +304,13 @@ def add_services(wl: Workload, n_services: int, eps_per_service: int, seed=RULE_
             ips[i] = addrs[int(nrng.integers(len(addrs)))]  # the packets' destination
             ports[i] = port
         wl.node_port_addresses = list(NODE_PORT_ADDRESSES)
+    wl.affinity_groups = set()
+    if affinity_frac > 0:  # (a generator of its own: at 0 every seed yields the workload it always did)
+        arng = np.random.default_rng(seed + 29)
+        for i in np.nonzero(arng.random(n_services) < affinity_frac)[0]:
+            s = wl.services[i]
+            s["affinity_timeout"] = int(affinity_timeout)
+            wl.affinity_groups.add(s["local_group_id"] if s["traffic_policy_local"] else s["cluster_group_id"])
     wl.svc_meta = {"ip": ips.astype(np.uint32), "port": ports.astype(np.uint16),
                    "proto": np.array([SVC_PROTOS[k][1] for k in pk], np.uint8)}
     wl.svc_frac = svc_frac
@@ -314,8 +325,12 @@ def install_services(clf, wl: Workload):
         clf.install_pod(_ip(ip), port)
     if getattr(wl, "node_port_addresses", None):
         clf.set_node_port_addresses(wl.node_port_addresses, *fam)
+    aff = getattr(wl, "affinity_groups", ())
     for gid, eps in wl.groups.items():
-        clf.install_service_group(gid, eps)
+        if gid in aff:
+            clf.install_service_group(gid, eps, True)
+        else:
+            clf.install_service_group(gid, eps)
     for proto, eps in wl.endpoint_flows:
         clf.install_endpoint_flows(proto, eps, *fam)
     for cfg in wl.services:

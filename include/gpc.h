@@ -143,7 +143,10 @@ typedef struct gpc_config {
                                     finished; > 0 = that many calls in flight per stream; < 0 = off
                                     (never blocks: a caller that keeps its stream's queue full may
                                     then delay gpc_commit's publish behind its blocking launches) */
-  int32_t reserved[1];
+  int32_t session_affinity;      /* sessionAffinity: ClientIP for IPv4 Services (the learned-flow table of OVS's
+                                    SessionAffinity table, kept on the device): 0 = off (configs with
+                                    affinity_timeout are rejected), n in [8, 26] = a table of 2^n entries
+                                    (32 B each) per device slot; anything else fails gpc_create          */
 } gpc_config;
 
 /* Order a grouped batch is classified in, inside every tile of 16384 packets (results never depend
@@ -268,6 +271,9 @@ typedef struct gpc_lb_result {
                                     serviceNoEndpointFlow -> SvcReject packet-in)               */
 #define GPC_LB_DNAT 0x4          /* an EndpointDNAT flow rewrote the destination               */
 #define GPC_LB_REMOTE 0x8        /* RemoteEndpointRegMark: the Endpoint is on another Node      */
+#define GPC_LB_AFFINITY 0x10     /* session affinity: the Endpoint came from a learned entry or from the
+                                    packet of this batch that learned it                         */
+#define GPC_LB_LEARNED 0x20      /* ... and this packet created the entry                         */
 /* The same for an IPv6 packet (optional output of gpc_classify6_lb), 32 bytes, 16-byte aligned. */
 typedef struct gpc_lb_result6 {
   uint8_t endpoint_ip[16];       /* selected Endpoint (xxreg3), network byte order; 0 if none */
@@ -413,8 +419,15 @@ int gpc_install_endpoint_flows(gpc_ctx* ctx, uint8_t protocol, uint8_t family, c
 int gpc_uninstall_endpoint_flows(gpc_ctx* ctx, uint8_t protocol, uint8_t family, const gpc_endpoint* eps, size_t n);
 /* InstallServiceFlows(*types.ServiceConfig) error                           client.go:790
  * Supported: ClusterIP / LoadBalancer / ExternalIP / NodePort Services (optionally Local traffic
- * policy) without session affinity, DSR, multi-cluster nesting or the external + Local
- * short-circuit; other configs -GPC_EINVAL. A NodePort Service (is_nodeport; the caller passes the
+ * policy) without DSR, multi-cluster nesting or the external + Local short-circuit; other configs
+ * -GPC_EINVAL. Session affinity (affinity_timeout = T > 0): IPv4 configs of a context created with
+ * gpc_config.session_affinity; the ServiceLB flow then loads EpToLearnRegMark and a priority-190
+ * learn flow (serviceLearnFlow, pipeline.go:2316-2371; cookie | TrafficPolicyGroupID) is realized
+ * beside it. Its learned flows live in the device's affinity table: keyed by (this install, client
+ * nw_src, packet nw_dst), value = the Endpoint, hard timeout T seconds of gpc_set_affinity_clock.
+ * Every install of an affinity config gets a fresh install id (24 bits, never reused), so a
+ * reinstall or uninstall orphans the entries learned so far (delete_learned). A family-6 config with
+ * affinity_timeout, or any with session_affinity == 0: -GPC_EINVAL. A NodePort Service (is_nodeport; the caller passes the
  * virtual NodePort DNAT IP 169.254.0.252 as its ip, as the proxier does) matches packets to the
  * NodePort addresses (gpc_set_node_port_addresses) by protocol and port (pipeline.go:2381-2387).
  * Both families take the same shapes: a family-6 config, Endpoint or Pod realizes the tcp6 / udp6 /
@@ -437,6 +450,31 @@ int gpc_uninstall_pod(gpc_ctx* ctx, const uint8_t* ip, uint8_t family);
  * and leaves the other family's flows alone; n = 0 removes them (proxyAll off). Family 6: ::1 is
  * skipped, the virtual IP is fc01::aabb:ccdd:eefe. */
 int gpc_set_node_port_addresses(gpc_ctx* ctx, const uint8_t* ips, uint8_t family, size_t n);
+/* Session affinity (gpc_config.session_affinity). The clock the learned entries' hard timeouts are
+ * measured on, in seconds; captured by every launch. Monotonic: a value below the last one set is
+ * -GPC_EINVAL. While never set the library reads CLOCK_MONOTONIC. */
+int gpc_set_affinity_clock(gpc_ctx* ctx, uint32_t seconds);
+typedef struct gpc_affinity_counts {
+  uint64_t slots;     /* entries of the slot's table (2^session_affinity; 0: feature off)            */
+  uint64_t live;      /* entries live at the current clock, counted by this call                      */
+  uint64_t learned;   /* entries created or overwritten (packets flagged GPC_LB_LEARNED), cumulative  */
+  uint64_t hits;      /* packets flagged GPC_LB_AFFINITY without GPC_LB_LEARNED, cumulative           */
+  uint64_t overflow;  /* +new packets whose key found no free slot (not learned), cumulative          */
+  uint64_t sweeps;    /* sweep launches (expired entries cleared), cumulative                         */
+} gpc_affinity_counts;
+/* Synchronizes the slot's device. The counters restart with gpc_replay (which clears the table). */
+int gpc_affinity_stats(gpc_ctx* ctx, uint32_t slot, gpc_affinity_counts* out);
+typedef struct gpc_affinity_entry { /* one learned flow */
+  uint32_t install_id;             /* the gpc_install_service_flows call it belongs to (1, 2, ... in call order) */
+  uint32_t src;                    /* client address (NXM_OF_IP_SRC)                                   */
+  uint32_t dst;                    /* Service IP or NodePort address (NXM_OF_IP_DST; 0: no longer known) */
+  uint32_t endpoint_ip;
+  uint32_t endpoint_port;          /* reg4[0..15] | GPC_LB_REMOTE << 16                                */
+  uint32_t expires;                /* clock value from which the entry is dead                          */
+} gpc_affinity_entry;
+/* Test hook: a host copy of the live entries of a slot's table (synchronizes the device; copies the
+ * whole table). *n = live entries; more than cap: -GPC_ERANGE. */
+int gpc_debug_affinity_table(gpc_ctx* ctx, uint32_t slot, gpc_affinity_entry* buf, size_t cap, size_t* n);
 /* ovs-ofctl dump-groups style text of the realized groups, '\n' separated. */
 int gpc_dump_groups(gpc_ctx* ctx, char* buf, size_t cap, size_t* needed);
 
@@ -477,13 +515,28 @@ int gpc_classify(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* o
  * 5-tuple), are DNATed by the EndpointDNAT flow and continue to the policy stages with nw_dst /
  * tp_dst = the Endpoint, ct_nw_dst = the Service IP, reg7 = the group id and reg1 / destination
  * from the Pod map. lb_out (device, n entries, may be NULL) receives the selection. gpc_classify
- * runs the same stage (it just does not write lb_out). */
+ * runs the same stage (it just does not write lb_out).
+ * Session affinity (an affinity Service is committed and the context has a table): per packet to
+ * such a Service with Endpoints, in batch order -- (1) a live entry of its key whose Endpoint still
+ * belongs to the Service gives that Endpoint (DNAT flag, out_port, destination from the current
+ * image); (2) else a +new packet (ct_state & GPC_CT_NEW) takes its hash choice and creates or
+ * overwrites the entry, expiring at clock + timeout (a hit never refreshes it); (3) else the
+ * packet takes its hash choice and learns nothing. So in one batch the first +new packet of a key
+ * without a live entry decides for every later packet of the key; earlier ones keep their own
+ * choice. The table belongs to the device slot: it survives commits and compactions, gpc_replay
+ * clears it; batches that touch it are ordered on the slot by an event, whatever their streams. A
+ * caller that spreads packets over slots must shard by client address. A key that finds no free
+ * slot is not learned (gpc_affinity_stats overflow). Two launches (aff_learn, aff_resolve; aff_sweep
+ * once per clock value) run in front of the policy launches; without an affinity Service the
+ * launches are those of a context without the feature. */
 int gpc_classify_lb(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out, gpc_lb_result* lb_out,
                     int32_t count, void* stream);
 /* Traceflow-style readback (traceflow/packetin.go:211-270 reads the verdict registers
  * back, ovsctl.go:91-183 wraps ofproto/trace): packet 0 of the HOST columns `pkt` through the
  * current epoch on the device, Service stage included; out[2] = its verdicts (as gpc_classify),
- * steps[0..*n_steps) = each rule table the walk evaluated, in order. Synchronous; debug path. */
+ * steps[0..*n_steps) = each rule table the walk evaluated, in order. Synchronous; debug path.
+ * Session affinity: the trace reads the table and never learns (a live entry gives the learned
+ * Endpoint, otherwise the hash choice). */
 int gpc_trace(gpc_ctx* ctx, const gpc_pkt_soa* pkt, gpc_verdict* out, gpc_lb_result* lb_out, gpc_trace_step* steps,
               size_t cap, size_t* n_steps);
 /* IPv6 packets (pkts->src6 / dst6 columns) against the IPv6 half of the rule set (the ipv6_* /
@@ -568,7 +621,8 @@ int gpc_stream_epoch(gpc_ctx* ctx, void* stream, uint64_t* epoch);
  * gpc_launch_times before it comes round again is overwritten and counted in `dropped`);
  * slots = 0 (the default) records nothing. */
 typedef struct gpc_launch_time {
-  char kernel[32];   /* "group_tiles", "classify_egress", "classify_ingress", "classify_both", "unpermute" */
+  char kernel[32];   /* "group_tiles", "classify_egress", "classify_ingress", "classify_both", "unpermute",
+                        "v6_codes", "v6_lb", "aff_learn", "aff_resolve", "aff_sweep" */
   uint32_t launches; /* launches of that kernel since the previous gpc_launch_times */
   uint32_t dropped;  /* event sets overwritten before they were read (all kinds) */
   double total_ms;   /* summed HIP-event durations */

@@ -1,0 +1,127 @@
+"""Loader for the TEST-ONLY host run of the session-affinity passes (tests/csrc/emu_aff.cpp) and the
+emulated classification with affinity Services: a host affinity table driven exactly as the library
+drives the device one (api.cpp aff_prepare: reset on first use, a sweep of the expired entries
+whenever the clock has moved since the last one, one launch sequence number per batch), the learn
+and resolve bodies of core.hpp over the batch, packets of a Service without Endpoints set aside
+(rejected in EndpointDNAT), the existing emulation of the policy stages on the rewritten columns."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from antrea_amd import gpc
+from tests import emu
+
+LIB = os.path.join(emu.OUT, "libgpc_emu_aff.so")
+_lib = None
+SWEEP_EXPIRED, SWEEP_RESET, SWEEP_BIDS, SWEEP_COUNT = 0, 1, 2, 3  # core.hpp aff_sweep_slot modes
+LEARNED, HITS, OVERFLOW, LIVE = 0, 1, 2, 3                       # core.hpp AffCounter
+
+
+def load():
+    global _lib
+    if _lib is not None:
+        return _lib
+    src = os.path.join(emu.HERE, "csrc", "emu_aff.cpp")
+    deps = [src, os.path.join(emu.ROOT, "antrea_amd", "csrc", "core.hpp"), os.path.join(emu.ROOT, "include", "gpc.h")]
+    os.makedirs(emu.OUT, exist_ok=True)
+    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
+        tmp = "%s.%d.tmp" % (LIB, os.getpid())  # renamed into place: parallel workers never load a half-written file
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + os.path.join(emu.ROOT, "include"),
+                        "-I" + os.path.join(emu.ROOT, "antrea_amd", "csrc"), src, "-o", tmp], check=True)
+        os.replace(tmp, LIB)
+    _lib = C.CDLL(LIB)
+    _lib.emu_aff_sweep.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
+    _lib.emu_aff_image.argtypes = [C.c_void_p]
+    _lib.emu_aff_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int,
+                                   C.POINTER(gpc.gpc_pkt_soa), C.c_size_t] + [C.c_void_p] * 7
+    return _lib
+
+
+def install_ids(clf):
+    """The install ids realized in the committed Service image (SvcHdr aff_off / n_svc words)."""
+    b = C.POINTER(C.c_uint32)()
+    n = C.c_size_t()
+    gpc._check(clf.lib.gpc_debug_service_image(clf.h, C.byref(b), C.byref(n)), "gpc_debug_service_image")
+    if not n.value or not b[11]:
+        return set()
+    return {int(b[b[10] + i]) for i in range(b[3])} - {0}
+
+
+class Table:
+    """The affinity table of one device slot, on the host."""
+
+    def __init__(self, log2):
+        self.log2 = log2
+        self.tab = np.zeros(8 << log2, np.uint32)
+        self.ctr = np.zeros(4, np.uint64)
+        self.seq = self.swept = self.sweeps = 0
+        self.fresh = True
+
+    def _sweep(self, now, mode):
+        load().emu_aff_sweep(self.tab.ctypes.data, self.log2, self.ctr.ctypes.data, now, mode)
+
+    def stage(self, clf, cols, now, read_only=False):
+        """The Service stage alone: (rewritten columns, lb results (n,) LB_DTYPE, no-Endpoint mask)."""
+        svc = clf.debug_service_image()
+        assert svc and load().emu_aff_image(svc), "no Service image with an affinity Service committed"
+        if not read_only:
+            if self.fresh:
+                self._sweep(now, SWEEP_RESET)
+                self.fresh, self.swept = False, now
+            elif now > self.swept:
+                self._sweep(now, SWEEP_EXPIRED)
+                self.swept = now
+                self.sweeps += 1
+            self.seq += 1
+        elif self.fresh:
+            self._sweep(now, SWEEP_RESET)
+            self.fresh, self.swept = False, now
+        soa, keep, n = gpc.pkt_soa_host(cols)
+        dst, dport, out_port = np.zeros(n, np.uint32), np.zeros(n, np.uint16), np.zeros(n, np.uint32)
+        svc_group, dest = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        lb = np.zeros(n, gpc.LB_DTYPE)
+        noep = np.zeros(n, np.uint8)
+        load().emu_aff_batch(svc, self.tab.ctypes.data, self.log2, self.ctr.ctypes.data, now, self.seq, int(read_only),
+                             C.byref(soa), n, *[a.ctypes.data for a in (dst, dport, out_port, svc_group, dest, lb, noep)])
+        out = dict(cols, dst=dst, dport=dport, out_port=out_port, svc_group=svc_group, dest=dest)
+        out.setdefault("ct_dst", np.ascontiguousarray(cols["dst"], np.uint32))  # ct_nw_dst: the pre-NAT destination
+        return out, lb, noep.astype(bool)
+
+    def classify(self, clf, cols, now, counters=None, lb=None, read_only=False):
+        """Emulated verdicts (n, 2) of the epoch last committed by `clf` at clock `now`. An image
+        without an affinity Service takes the plain emulation, as the library takes its plain launches."""
+        n = len(cols["src"])
+        svc = clf.debug_service_image()
+        if not (svc and load().emu_aff_image(svc)):
+            return emu.classify(clf, cols, counters, lb)
+        rw, res, noep = self.stage(clf, cols, now, read_only)
+        if lb is not None:
+            lb[:n] = res
+        out = np.zeros((n, 2), dtype=gpc.VERDICT_DTYPE)
+        out[noep, 0] = (0, gpc.ACT_NAMES.index("REJECT"), gpc.VTABLE_ENDPOINT_DNAT, 0, 0)
+        live = ~noep
+        if live.any():
+            blob, nw, hdr, _ = clf.debug_image()
+            pool, _, jhdr = clf.debug_epoch()
+            soa, keep, m = gpc.pkt_soa_host({k: np.ascontiguousarray(v[live]) for k, v in rw.items()})
+            part = np.zeros(2 * m, dtype=gpc.VERDICT_DTYPE)
+            cnt = emu._Counters(counters)
+            emu.load().emu_classify(blob, hdr, pool, jhdr, None, C.byref(soa), m, part.ctypes.data, None, cnt.ptr)
+            cnt.publish()
+            out[live] = part.reshape(m, 2)
+        return out
+
+    def live(self, now):
+        """Live entries as sorted (src, dst id word, endpoint ip, endpoint port | flags, expires) --
+        the id word is (install id << 8 | NodePort address id)."""
+        t = self.tab.reshape(-1, 8)
+        m = ((t[:, 0] | t[:, 1]) != 0) & (now < t[:, 6])
+        return sorted((int(r[0]), int(r[1]), int(r[4]), int(r[5]), int(r[6])) for r in t[m])
+
+    def stats(self, now):
+        self.ctr[LIVE] = 0
+        self._sweep(now, SWEEP_COUNT)
+        return {"slots": 1 << self.log2, "live": int(self.ctr[LIVE]), "learned": int(self.ctr[LEARNED]),
+                "hits": int(self.ctr[HITS]), "overflow": int(self.ctr[OVERFLOW]), "sweeps": self.sweeps}

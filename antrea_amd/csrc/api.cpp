@@ -1372,6 +1372,15 @@ int gpc_debug_affinity_table(gpc_ctx* ctx, uint32_t slot, gpc_affinity_entry* bu
   return k > cap ? -GPC_ERANGE : GPC_OK;
 }
 
+int gpc_debug_set_affinity_seq(gpc_ctx* ctx, uint32_t slot, uint32_t seq) {
+  if (!ctx || slot >= ctx->dev.size()) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> d(ctx->data);
+  DevState& D = ctx->dev[slot];
+  if (!ctx->cfg.session_affinity || !D.d_aff) return -GPC_EINVAL;  // (a table's first use restarts the sequence)
+  D.aff_seq = seq;
+  return GPC_OK;
+}
+
 int gpc_classify(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, int32_t count, void* stream) {
   return gpc_classify_on(ctx, 0, pk, n, out, nullptr, count, stream);
 }

@@ -144,7 +144,7 @@ EXPORTS = ["gpc_create", "gpc_destroy", "gpc_initialize", "gpc_install_rule", "g
            "gpc_set_launch_timing", "gpc_launch_times", "gpc_create_multi", "gpc_n_devices", "gpc_classify_on",
            "gpc_classify6_on", "gpc_classify_host_on", "gpc_counters_on", "gpc_debug_epoch6", "gpc_debug_fail_uploads",
            "gpc_classify6_lb", "gpc_classify6_lb_on", "gpc_classify6_host_lb", "gpc_debug_service_image6",
-           "gpc_set_affinity_clock", "gpc_affinity_stats", "gpc_debug_affinity_table"]
+           "gpc_set_affinity_clock", "gpc_affinity_stats", "gpc_debug_affinity_table", "gpc_debug_set_affinity_seq"]
 
 _lib = None
 
@@ -223,6 +223,7 @@ def load(path: str = LIB_PATH):
     lib.gpc_set_affinity_clock.argtypes = [vp, C.c_uint32]
     lib.gpc_affinity_stats.argtypes = [vp, C.c_uint32, C.POINTER(gpc_affinity_counts)]
     lib.gpc_debug_affinity_table.argtypes = [vp, C.c_uint32, vp, sz, C.POINTER(sz)]
+    lib.gpc_debug_set_affinity_seq.argtypes = [vp, C.c_uint32, C.c_uint32]
     lib.gpc_strerror.argtypes = [i32]
     lib.gpc_strerror.restype = C.c_char_p
     _lib = lib
@@ -634,6 +635,10 @@ class Classifier:
             _check(self.lib.gpc_debug_affinity_table(self.h, int(slot), buf.ctypes.data, n.value, C.byref(n)),
                    "gpc_debug_affinity_table")
         return buf
+
+    def debug_set_affinity_seq(self, seq, slot=0):
+        """Test hook: the launch sequence number of the slot's last affinity batch."""
+        _check(self.lib.gpc_debug_set_affinity_seq(self.h, int(slot), int(seq)), "gpc_debug_set_affinity_seq")
 
     def dump_groups(self) -> List[str]:
         need = C.c_size_t()

@@ -475,6 +475,10 @@ typedef struct gpc_affinity_entry { /* one learned flow */
 /* Test hook: a host copy of the live entries of a slot's table (synchronizes the device; copies the
  * whole table). *n = live entries; more than cap: -GPC_ERANGE. */
 int gpc_debug_affinity_table(gpc_ctx* ctx, uint32_t slot, gpc_affinity_entry* buf, size_t cap, size_t* n);
+/* Test hook: the launch sequence number of the slot's last affinity batch (32 bits, one per batch;
+ * the bid words are reset when it is about to wrap), so a test can cross the wrap without 2^32
+ * batches. -GPC_EINVAL before the slot's table exists (its first use restarts the sequence). */
+int gpc_debug_set_affinity_seq(gpc_ctx* ctx, uint32_t slot, uint32_t seq);
 /* ovs-ofctl dump-groups style text of the realized groups, '\n' separated. */
 int gpc_dump_groups(gpc_ctx* ctx, char* buf, size_t cap, size_t* needed);
 

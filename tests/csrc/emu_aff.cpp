@@ -5,6 +5,7 @@
 // emulation (emu.cpp emu_classify, no Service image) on them. Never linked into libgpc.so.
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "core.hpp"
 #include "gpc.h"
@@ -23,7 +24,33 @@ struct AffOpsHost {  // the atomics shim of a single thread
   }
   static void count(unsigned long long* c, bool pred) { *c += pred ? 1 : 0; }
 };
+
+// The same single thread, but every packet's plain loads of the learn pass (aff_find, the entry's
+// validity) see the table as it was before the pass, as a device lane may whose neighbours' claims
+// have not become visible yet: aff_learn runs over a snapshot of the table, and the atomics -- whose
+// addresses it derives from the snapshot -- are redirected to the table itself. Entries do not change
+// during the learn pass, so only the key words differ between the two. The result must be that of
+// the plain run: ownership is decided from what the compare-and-swap returns, never from the loads.
+struct AffOpsStale {
+  static inline uintptr_t snapshot = 0, table = 0;  // addresses of the two copies
+  static uint64_t* real(uint64_t* p) { return reinterpret_cast<uint64_t*>(table + (reinterpret_cast<uintptr_t>(p) - snapshot)); }
+  static uint64_t cas(uint64_t* p, uint64_t expect, uint64_t v) { return AffOpsHost::cas(real(p), expect, v); }
+  static void min(uint64_t* p, uint64_t v) { AffOpsHost::min(real(p), v); }
+  static void count(unsigned long long* c, bool pred) { AffOpsHost::count(c, pred); }
+};
 }  // namespace
+
+// The four candidate slots of the key (install id, NodePort address id, client address) in a table
+// of 2^log2 slots, in scan order: the product's own hash, for tests that build colliding keys.
+extern "C" int emu_aff_candidates(uint32_t install, uint32_t np_id, uint32_t src, uint32_t log2, uint32_t* out) {
+  aff_candidates(aff_key(install, np_id, src), log2, out);
+  return 0;
+}
+// The same for n consecutive client addresses from `src` on: out[4 * n].
+extern "C" int emu_aff_candidates_range(uint32_t install, uint32_t np_id, uint32_t src, uint32_t n, uint32_t log2, uint32_t* out) {
+  for (uint32_t i = 0; i < n; i++) aff_candidates(aff_key(install, np_id, src + i), log2, out + 4 * size_t(i));
+  return 0;
+}
 
 extern "C" int emu_aff_sweep(uint32_t* tab, uint32_t log2, unsigned long long* ctr, uint32_t now, uint32_t mode) {
   const AffTable t{tab, log2, ctr};
@@ -35,16 +62,25 @@ extern "C" int emu_aff_sweep(uint32_t* tab, uint32_t log2, unsigned long long* c
 extern "C" int emu_aff_image(const uint32_t* svc) { return svc && reinterpret_cast<const SvcHdr*>(svc)->n_aff != 0; }
 
 // The learn pass over the whole batch, then the resolve pass (as the two kernels run). lb_out: n
-// gpc_lb_result (may be null); noep: n flags.
+// gpc_lb_result (may be null); noep: n flags. stale_find: the learn pass with AffOpsStale.
 extern "C" int emu_aff_batch(const uint32_t* svc, uint32_t* tab, uint32_t log2, unsigned long long* ctr, uint32_t now,
-                             uint32_t seq, int read_only, const gpc_pkt_soa* pk, size_t n, uint32_t* dst_out,
+                             uint32_t seq, int read_only, int stale_find, const gpc_pkt_soa* pk, size_t n, uint32_t* dst_out,
                              uint16_t* dport_out, uint32_t* out_port_out, uint32_t* svc_group_out, uint8_t* dest_out,
                              uint32_t* lb_out, uint8_t* noep) {
   const AffTable t{tab, log2, ctr};
-  if (!read_only)
+  if (!read_only && stale_find) {
+    std::vector<uint32_t> snap(tab, tab + (size_t(kAffSlotWords) << log2));
+    const AffTable before{snap.data(), log2, ctr};
+    AffOpsStale::snapshot = reinterpret_cast<uintptr_t>(snap.data());
+    AffOpsStale::table = reinterpret_cast<uintptr_t>(tab);
+    for (size_t i = 0; i < n; i++)
+      aff_learn<AffOpsStale>(svc, before, now, seq, uint32_t(i), pk->src[i], pk->dst[i], pk->dport[i], pk->proto[i],
+                             pk->ct_state ? pk->ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK));
+  } else if (!read_only) {
     for (size_t i = 0; i < n; i++)
       aff_learn<AffOpsHost>(svc, t, now, seq, uint32_t(i), pk->src[i], pk->dst[i], pk->dport[i], pk->proto[i],
                             pk->ct_state ? pk->ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK));
+  }
   for (size_t i = 0; i < n; i++) {
     uint32_t dst = pk->dst[i], dport = pk->dport[i], out_port = pk->out_port[i];
     uint32_t svc_group = pk->svc_group ? pk->svc_group[i] : 0u, dest = pk->dest ? pk->dest[i] : 0u;

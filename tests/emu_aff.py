@@ -1,7 +1,8 @@
 """Loader for the TEST-ONLY host run of the session-affinity passes (tests/csrc/emu_aff.cpp) and the
 emulated classification with affinity Services: a host affinity table driven exactly as the library
 drives the device one (api.cpp aff_prepare: reset on first use, a sweep of the expired entries
-whenever the clock has moved since the last one, one launch sequence number per batch), the learn
+whenever the clock has moved since the last one, one launch sequence number per batch, the bid words
+reset when the 32-bit sequence would wrap), the learn
 and resolve bodies of core.hpp over the batch, packets of a Service without Endpoints set aside
 (rejected in EndpointDNAT), the existing emulation of the policy stages on the rewritten columns."""
 import ctypes as C
@@ -34,26 +35,49 @@ def load():
     _lib = C.CDLL(LIB)
     _lib.emu_aff_sweep.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     _lib.emu_aff_image.argtypes = [C.c_void_p]
-    _lib.emu_aff_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int,
+    _lib.emu_aff_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
                                    C.POINTER(gpc.gpc_pkt_soa), C.c_size_t] + [C.c_void_p] * 7
+    _lib.emu_aff_candidates.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    _lib.emu_aff_candidates_range.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     return _lib
 
 
-def install_ids(clf):
-    """The install ids realized in the committed Service image (SvcHdr aff_off / n_svc words)."""
+def candidates(install, src, log2, np_id=0, n=None):
+    """core.hpp aff_candidates of the key (install id, NodePort address id, client address): its four
+    candidate slots in scan order, (4,) uint32; with `n`, of the n consecutive clients from src on, (n, 4)."""
+    out = np.zeros((1 if n is None else n, 4), np.uint32)
+    if n is None:
+        load().emu_aff_candidates(install, np_id, src, log2, out.ctypes.data)
+        return out[0]
+    load().emu_aff_candidates_range(install, np_id, src, n, log2, out.ctypes.data)
+    return out
+
+
+def affinity_services(clf):
+    """The affinity Services of the committed Service image as (install id, group id, timeout), in the
+    order of the Service records (SvcHdr svc_off / n_svc; the install ids are the n_svc words at aff_off)."""
     b = C.POINTER(C.c_uint32)()
     n = C.c_size_t()
     gpc._check(clf.lib.gpc_debug_service_image(clf.h, C.byref(b), C.byref(n)), "gpc_debug_service_image")
     if not n.value or not b[11]:
-        return set()
-    return {int(b[b[10] + i]) for i in range(b[3])} - {0}
+        return []
+    rec = lambda i: b[2] + 4 * i  # {first endpoint, n_ep | slot_log2 << 24, group id, flags | timeout << 16}
+    return [(int(b[b[10] + i]), int(b[rec(i) + 2]), int(b[rec(i) + 3]) >> 16) for i in range(b[3]) if b[b[10] + i]]
+
+
+def install_ids(clf):
+    """The install ids realized in the committed Service image."""
+    return {s[0] for s in affinity_services(clf)}
 
 
 class Table:
     """The affinity table of one device slot, on the host."""
 
-    def __init__(self, log2):
+    def __init__(self, log2, stale_find=False):
+        """stale_find: the learn pass's plain loads see the table as it was before the pass (emu_aff.cpp
+        AffOpsStale), the other extreme of what a device lane may see; the results must not differ."""
         self.log2 = log2
+        self.stale_find = stale_find
         self.tab = np.zeros(8 << log2, np.uint32)
         self.ctr = np.zeros(4, np.uint64)
         self.seq = self.swept = self.sweeps = 0
@@ -61,6 +85,11 @@ class Table:
 
     def _sweep(self, now, mode):
         load().emu_aff_sweep(self.tab.ctypes.data, self.log2, self.ctr.ctypes.data, now, mode)
+
+    def set_seq(self, seq):
+        """gpc_debug_set_affinity_seq: the launch sequence number of the last batch."""
+        assert not self.fresh, "a table's first use restarts the sequence"
+        self.seq = seq & 0xffffffff
 
     def stage(self, clf, cols, now, read_only=False):
         """The Service stage alone: (rewritten columns, lb results (n,) LB_DTYPE, no-Endpoint mask)."""
@@ -70,7 +99,10 @@ class Table:
             if self.fresh:
                 self._sweep(now, SWEEP_RESET)
                 self.fresh, self.swept = False, now
-            elif now > self.swept:
+            elif self.seq >= 0xfffffffe:  # the sequence wraps: the bid words start over
+                self._sweep(now, SWEEP_BIDS)
+                self.seq = 0
+            if now > self.swept:
                 self._sweep(now, SWEEP_EXPIRED)
                 self.swept = now
                 self.sweeps += 1
@@ -84,7 +116,7 @@ class Table:
         lb = np.zeros(n, gpc.LB_DTYPE)
         noep = np.zeros(n, np.uint8)
         load().emu_aff_batch(svc, self.tab.ctypes.data, self.log2, self.ctr.ctypes.data, now, self.seq, int(read_only),
-                             C.byref(soa), n, *[a.ctypes.data for a in (dst, dport, out_port, svc_group, dest, lb, noep)])
+                             int(self.stale_find), C.byref(soa), n, *[a.ctypes.data for a in (dst, dport, out_port, svc_group, dest, lb, noep)])
         out = dict(cols, dst=dst, dport=dport, out_port=out_port, svc_group=svc_group, dest=dest)
         out.setdefault("ct_dst", np.ascontiguousarray(cols["dst"], np.uint32))  # ct_nw_dst: the pre-NAT destination
         return out, lb, noep.astype(bool)

@@ -225,3 +225,81 @@ def test_small_table_overflows_and_reuses_swept_slots():
     table.classify(c, batch(5000, 100), 10 + 100, lb=np.zeros(100, gpc.LB_DTYPE))
     st = table.stats(110)
     assert st["overflow"] == over and st["live"] == 100
+
+
+# ------------------------------------------------------------------ the table under hash pressure
+# (tests/affinity_cases.py KeySet: keys that share buckets in a table of 256 slots.) Emulation ==
+# model for three shuffles of every batch: which slot a key lands in depends on the order, the results
+# must not. Shuffle 2 runs the learn pass with stale finds (emu_aff.cpp AffOpsStale). The per-rule
+# counters are the device's against the emulation's in the GPU tier; the model has none.
+ORDERS = [0, 1, 2]
+
+
+@pytest.fixture(scope="module")
+def pressure_keys():
+    wl, clf, svcs = ac.make_pressure_product()
+    emu.commit_host(clf)
+    return ac.KeySet(clf)
+
+
+def _pressure(order):
+    wl, clf, svcs = ac.make_pressure_product()
+    emu.commit_host(clf)
+    table = emu_aff.Table(ac.P_LOG2, stale_find=order == 2)
+    return wl, clf, svcs, table
+
+
+def test_candidates_are_the_products_hash(pressure_keys):
+    """emu_aff.candidates against the slots the emulated learn pass really uses, and the clusters'
+    shapes."""
+    ks = pressure_keys
+    assert ks.install[0] != ks.install[1] and all(ks.install)
+    assert (emu_aff.candidates(ks.install[1], ac.P_NETS[1] + 77, ac.P_LOG2) == ks.cand[1][77]).all()
+    wl, clf, svcs, table = _pressure(0)
+    keys = ks.spread(1, 40)
+    table.classify(clf, ac.key_batch(wl, svcs, keys, 3, per_key=2, established=0.0), 10)
+    assert all(ks.slot_of(table, k) == [k.c[0]] for k in keys)  # nothing in the way: the first candidate
+    a1, a2, b1, b2 = ks.shared
+    assert len({k.c[0] for k in ks.shared}) == 1 and len({k.c[2] for k in ks.shared}) == 4
+    assert [k.svc for k in ks.shared] == [0, 0, 1, 1] and [k.svc for k in ks.identical] == [0, 0, 1, 1, 1, 1]
+    d, e = ks.degenerate
+    assert d.c[:2] == d.c[2:] and e.c[:2] == d.c[:2] and e.c[2] != e.c[0]
+    assert sum(1 for k in ks.exact_keys() if k.c[0] == d.c[0]) == 2
+    f, g = ks.chain
+    assert f.c[2:] == g.c[:2] and len({f.c[0], f.c[2], g.c[2]}) == 3
+    assert len(ks.background) == 30 and all(len(ac.neighbours(k, ks.exact_keys())) == 1 for k in ks.background)
+    assert len(ac.neighbours(a1, ks.exact_keys())) == 3 and len(ac.neighbours(ks.identical[0], ks.identical)) == 5
+
+
+@pytest.mark.parametrize("order", ORDERS)
+def test_colliding_keys_in_one_batch(pressure_keys, order):
+    wl, clf, svcs, table = _pressure(order)
+    second = ac.case_collisions(wl, clf, svcs, pressure_keys, table, _emu_runner(clf, table), order)
+    assert set(second) & set(pressure_keys.shared)
+
+
+@pytest.mark.parametrize("order", ORDERS)
+def test_live_key_behind_an_emptied_bucket(pressure_keys, order):
+    wl, clf, svcs, table = _pressure(order)
+    ac.case_emptied_bucket(wl, clf, svcs, pressure_keys, table, _emu_runner(clf, table), lambda: emu.commit_host(clf), order)
+
+
+@pytest.mark.parametrize("order", ORDERS)
+def test_full_bucket_forced_order(pressure_keys, order):
+    wl, clf, svcs, table = _pressure(order)
+    ac.case_full_bucket_forced(wl, clf, svcs, pressure_keys, _emu_runner(clf, table), order)
+
+
+@pytest.mark.parametrize("order", ORDERS)
+def test_launch_sequence_wrap(pressure_keys, order):
+    wl, clf, svcs, table = _pressure(order)
+    ac.case_sequence_wrap(wl, clf, svcs, pressure_keys, table, _emu_runner(clf, table), table.set_seq, order)
+
+
+def test_set_affinity_seq_needs_a_table():
+    """gpc_debug_set_affinity_seq: a bad slot, the feature off, or no table yet (nothing classified on
+    the slot: the table's first use restarts the sequence) is GPC_EINVAL."""
+    for log2, slot in ((8, 0), (8, 1), (0, 0)):
+        c = gpc.Classifier(session_affinity=log2)
+        assert c.lib.gpc_debug_set_affinity_seq(c.h, slot, 0xfffffffc) == -gpc.GPC_EINVAL
+    assert c.lib.gpc_debug_set_affinity_seq(None, 0, 1) == -gpc.GPC_EINVAL

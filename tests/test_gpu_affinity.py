@@ -3,8 +3,9 @@ aff_learn_kernel / aff_resolve_kernel over the slot's affinity table, the policy
 rewritten columns). Device == model (tests/affinity_model.py: the realized learn flows executed
 serially) == host emulation of the same core.hpp bodies (tests/emu_aff.py), exactly: verdicts, LB
 results with the two affinity flag bits, the live entries, gpc_affinity_stats and the per-rule
-counters. Every equality test asserts overflow == 0 (tables of 2^12 slots for a few hundred keys: the
-emulation shows the same on the CPU tier); the capacity test checks properties instead."""
+counters. Every equality test asserts overflow == 0 (tables of 2^12 slots for a few hundred keys, or
+key sets that cannot overflow whatever the order: the emulation shows the same on the CPU tier) or an
+overflow count the batch's order forces; the capacity and racing tests check properties instead."""
 import copy
 import ipaddress
 
@@ -351,3 +352,132 @@ def test_gpu_no_affinity_service_no_affinity_launch():
     c.classify_host(b)
     kinds = set(c.launch_times())
     assert {"aff_learn", "aff_resolve", "aff_sweep"} <= kinds, kinds
+
+
+# ------------------------------------------------------------------ the table under hash pressure
+# tests/affinity_cases.py KeySet: keys chosen with the product's hash to share buckets in a table of
+# 256 slots. Exact (device == emulation == model) wherever no arrival order can overflow or the order
+# is forced; properties where lanes race for a full bucket.
+@pytest.fixture(scope="module")
+def pressure_keys():
+    wl, c, svcs = ac.make_pressure_product()
+    c.commit()
+    return ac.KeySet(c)
+
+
+def _pressure(**kw):
+    wl, c, svcs = ac.make_pressure_product(**kw)
+    c.commit()
+    return wl, c, svcs, emu_aff.Table(ac.P_LOG2)
+
+
+def test_gpu_colliding_keys_in_one_batch(pressure_keys):
+    """38 keys x 64 packets, shuffled over ten blocks: four keys with one first bucket, a key whose two
+    buckets coincide and its neighbour, a chain, background pairs with identical candidates. Lanes of
+    different keys race for the same slots; which key gets which is open, the results are not."""
+    wl, c, svcs, table = _pressure()
+    second = ac.case_collisions(wl, c, svcs, pressure_keys, table, _runner(c, table), 0, dst_known=True)
+    assert len(second) >= 2 and c.affinity_stats()["overflow"] == 0
+
+
+def test_gpu_live_key_behind_an_emptied_bucket(pressure_keys):
+    wl, c, svcs, table = _pressure()
+    ac.case_emptied_bucket(wl, c, svcs, pressure_keys, table, _runner(c, table), c.commit, 0, dst_known=True)
+    assert c.affinity_stats()["overflow"] == 0
+
+
+def test_gpu_full_bucket_forced_order(pressure_keys):
+    wl, c, svcs, table = _pressure()
+    ac.case_full_bucket_forced(wl, c, svcs, pressure_keys, _runner(c, table), 0, dst_known=True)
+
+
+@pytest.mark.parametrize("per_key", [64, 1024])
+def test_gpu_racing_for_a_full_bucket(pressure_keys, per_key):
+    """Six keys with the same four candidate slots in one batch on an empty table (per_key = 1024: 24
+    blocks): which four keys get a slot is decided by the race, so properties, not equality. Each key
+    is all-or-nothing: a holder behaves as a key alone in the table would, a loser as if the Service
+    had no affinity."""
+    wl, c, svcs, _ = _pressure()
+    keys = pressure_keys.identical
+    cols = ac.key_batch(wl, svcs, keys, 231, per_key=per_key)
+    index = ac.key_index(cols, svcs, keys)
+    own = ac.own_choices(c, cols)
+    ac.check_spread(own, index)
+    new = (cols["ct_state"] & 1) != 0
+    c.set_affinity_clock(ac.T0)
+    _, lb = c.classify_host(cols, lb=True)
+    holders = [k for k in keys if ((lb["flags"][index[k]] & L) != 0).any()]
+    losers = [k for k in keys if k not in holders]
+    assert len(holders) == 4
+    bound = {}
+    for k in holders:
+        idx = index[k]
+        first = ac.first_new(cols, idx)
+        assert list(idx[(lb["flags"][idx] & L) != 0]) == [first]
+        after, before = idx[idx >= first], idx[idx < first]
+        assert (lb["endpoint_ip"][after] == own["endpoint_ip"][first]).all() and (lb["endpoint_port"][after] == own["endpoint_port"][first]).all()
+        assert ((lb["flags"][after] & A) != 0).all()
+        assert (lb[before] == own[before]).all() and ((lb["flags"][before] & (A | L)) == 0).all()
+        bound[k] = (int(own["endpoint_ip"][first]), int(own["endpoint_port"][first]))
+    for k in losers:
+        assert (lb[index[k]] == own[index[k]]).all() and ((lb["flags"][index[k]] & (A | L)) == 0).all()
+    lost_new = sum(int(new[index[k]].sum()) for k in losers)
+    st = c.affinity_stats()
+    assert lost_new > 0 and st["overflow"] == lost_new and st["learned"] == st["live"] == 4, st
+    dst = {k: int(ipaddress.ip_address(svcs[k.svc][0]["ip"])) for k in keys}
+    t = c.affinity_table()
+    assert sorted((int(e["src"]), int(e["dst"])) for e in t) == sorted((k.src, dst[k]) for k in holders)
+    # the same batch again: the holders hit, the same two keys find the bucket full again
+    c.set_affinity_clock(ac.T0 + 1)
+    _, lb2 = c.classify_host(cols, lb=True)
+    ac.check_all_hits(lb2, {k: index[k] for k in holders}, bound)
+    for k in losers:
+        assert (lb2[index[k]] == own[index[k]]).all()
+    st = c.affinity_stats()
+    assert st["overflow"] == 2 * lost_new and st["learned"] == st["live"] == 4, st
+    assert sorted((int(e["src"]), int(e["dst"])) for e in c.affinity_table()) == sorted((k.src, dst[k]) for k in holders)
+
+
+def test_gpu_launch_sequence_wrap(pressure_keys):
+    wl, c, svcs, table = _pressure()
+    with pytest.raises(gpc.GpcError) as e:  # no table yet: its first use would restart the sequence
+        c.debug_set_affinity_seq(5)
+    assert e.value.code == gpc.GPC_EINVAL
+
+    def set_seq(seq):
+        c.debug_set_affinity_seq(seq)
+        table.set_seq(seq)
+    ac.case_sequence_wrap(wl, c, svcs, pressure_keys, table, _runner(c, table), set_seq, 0, dst_known=True)
+    assert c.affinity_stats()["overflow"] == 0
+
+
+def test_gpu_tables_are_per_slot(pressure_keys):
+    """Two device slots on one GPU: what slot 0 learned is unknown to slot 1, which learns the same
+    batch again; each slot equals an emulated table of its own."""
+    wl, c, svcs, t0 = _pressure(devices=[0, 0])
+    t1 = emu_aff.Table(ac.P_LOG2)
+    keys = pressure_keys.shared + pressure_keys.chain + pressure_keys.degenerate
+    ac.check_no_overflow(keys)
+    cols = ac.key_batch(wl, svcs, keys, 241)
+    index = ac.key_index(cols, svcs, keys)
+    entries = lambda slot: sorted((int(e["src"]), int(e["install_id"]), int(e["endpoint_ip"]), int(e["endpoint_port"]),
+                                   int(e["expires"])) for e in c.affinity_table(slot))
+    emulated = lambda t, now: sorted((e[0], e[1] >> 8) + e[2:] for e in t.live(now))
+
+    def run(slot, table, batch, now):
+        c.set_affinity_clock(now)
+        got, lb = c.classify_host(batch, lb=True, slot=slot)
+        elb = np.zeros(len(lb), gpc.LB_DTYPE)
+        _cmp(got, table.classify(c, batch, now, lb=elb), batch)
+        assert (lb == elb).all(), slot
+        assert c.affinity_stats(slot) == table.stats(now) and entries(slot) == emulated(table, now), slot
+        return lb
+    lb0 = run(0, t0, cols, ac.T0)
+    bound = ac.learned_endpoints(cols, lb0, index)
+    assert c.affinity_stats(1)["learned"] == 0 and len(c.affinity_table(1)) == 0
+    lb1 = run(1, t1, cols, ac.T0)
+    assert (lb1 == lb0).all() and ac.learned_endpoints(cols, lb1, index) == bound  # its own LEARNED packets
+    assert c.affinity_stats(0)["learned"] == c.affinity_stats(1)["learned"] == len(keys)
+    again = ac.key_batch(wl, svcs, keys, 242)
+    ac.check_all_hits(run(0, t0, again, ac.T0 + 1), ac.key_index(again, svcs, keys), bound)
+    assert c.affinity_stats(0)["learned"] == len(keys) and c.affinity_stats(0)["overflow"] == c.affinity_stats(1)["overflow"] == 0

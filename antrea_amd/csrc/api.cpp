@@ -164,6 +164,26 @@ struct DevState {
   uint32_t aff_swept = 0;                        // clock value of the last sweep
   uint64_t aff_sweeps = 0;
   hipEvent_t aff_done = nullptr;                 // after the last table kernel queued on the slot
+  // The same for IPv6 Services (gpc_config.session_affinity6; core.hpp "IPv6 affinity table"): a
+  // table, sequence, sweep clock and event of its own.
+  struct Aff6State {
+    uint32_t* tab = nullptr;
+    unsigned long long* ctr = nullptr;
+    uint32_t seq = 0, swept = 0;
+    uint64_t sweeps = 0;
+    hipEvent_t done = nullptr;
+    void drop() {  // the slot's device is current
+      if (tab) (void)hipFree(tab);
+      if (ctr) (void)hipFree(ctr);
+      if (done) (void)hipEventDestroy(done);
+      tab = nullptr;
+      ctr = nullptr;
+      done = nullptr;
+      seq = swept = 0;
+      sweeps = 0;
+    }
+  } a6;
+  uint32_t aff6_bits = 64;                       // gpc_debug_set_affinity6_digest_bits
 };
 
 // Delta commits append the changed rules to the journal of the current base (image.hpp Journal).
@@ -695,6 +715,7 @@ int gpc_create_multi(const gpc_config* cfg, const int32_t* devices, size_t n, gp
   if (!cfg->ipv4_enabled && !cfg->ipv6_enabled) return -GPC_EINVAL;
   if (cfg->group_key < GPC_GROUP_KEY_AUTO || cfg->group_key > GPC_GROUP_KEY_SCAN) return -GPC_EINVAL;
   if (cfg->session_affinity && (cfg->session_affinity < 8 || cfg->session_affinity > 26)) return -GPC_EINVAL;
+  if (cfg->session_affinity6 && (cfg->session_affinity6 < 8 || cfg->session_affinity6 > 26)) return -GPC_EINVAL;
   for (size_t k = 0; k < n; k++)
     if (devices[k] < 0) return -GPC_EINVAL;
   try {
@@ -726,6 +747,7 @@ static void drop_slot(DevState& D) {
   D.aff_done = nullptr;
   D.aff_seq = D.aff_swept = 0;
   D.aff_sweeps = 0;
+  D.a6.drop();
   for (auto& kv : D.scratch) {
     (void)hipFree(kv.second.p);
     if (kv.second.done) (void)hipEventDestroy(kv.second.done);
@@ -745,7 +767,7 @@ void gpc_destroy(gpc_ctx* ctx) {
   ctx->comp.cv.notify_all();
   if (ctx->comp.th.joinable()) ctx->comp.th.join();
   for (DevState& D : ctx->dev) {
-    if (D.cur.base || D.d_counters || !D.retired.empty() || D.ustream || !D.marks.empty() || D.d_aff) {
+    if (D.cur.base || D.d_counters || !D.retired.empty() || D.ustream || !D.marks.empty() || D.d_aff || D.a6.tab) {
       (void)hipSetDevice(D.device);
       (void)hipDeviceSynchronize();
       drop_slot(D);
@@ -1087,6 +1109,7 @@ int gpc_replay(gpc_ctx* ctx) {
       std::swap(old[k].aff_done, D.aff_done);
       D.aff_seq = D.aff_swept = 0;
       D.aff_sweeps = 0;
+      std::swap(old[k].a6, D.a6);  // (D.a6 is now the fresh state of old[k])
       old[k].ustream = D.ustream;
     }
     ctx->cur_epoch = 0;
@@ -1140,6 +1163,7 @@ int gpc_replay(gpc_ctx* ctx) {
     if (!rc && !ctx->svc_blob.empty()) rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc);
     if (!rc && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
     if (!rc && !ctx->svc6_blob.empty()) rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6);
+    if (!rc && ne[k].svc6) ne[k].svc6->affinity = svc_has_affinity(ctx->svc6_blob);
     if (!rc && (hip_ok(hipMalloc(&nc[k], cap * kCounterBytes * (copies + 1))) ||
                 hip_ok(hipMemset(nc[k], 0, cap * kCounterBytes * (copies + 1)))))
       rc = -GPC_EDEV;
@@ -1381,6 +1405,141 @@ int gpc_debug_set_affinity_seq(gpc_ctx* ctx, uint32_t slot, uint32_t seq) {
   return GPC_OK;
 }
 
+// ---- the IPv6 table (gpc_config.session_affinity6): the same management over its own state
+static Aff6Table aff6_table(const gpc_ctx* ctx, const DevState& D) {
+  return Aff6Table{D.a6.tab, uint32_t(ctx->cfg.session_affinity6), D.a6.ctr,
+                   D.aff6_bits >= 64 ? ~0ull : (1ull << D.aff6_bits) - 1ull};
+}
+
+// aff_prepare for the slot's IPv6 table. Fills *al.
+static int aff6_prepare(gpc_ctx* ctx, DevState& D, hipStream_t st, LaunchMarks* marks, Aff6Launch* al) {
+  DevState::Aff6State& A = D.a6;
+  const uint32_t now = aff_now(ctx);
+  const bool fresh = !A.tab;
+  if (fresh) {
+    const size_t bytes = (size_t(kAff6SlotWords) * 4) << ctx->cfg.session_affinity6;
+    if (hip_ok(hipMalloc((void**)&A.tab, bytes))) {
+      (void)hipGetLastError();
+      A.tab = nullptr;
+      return -GPC_ENOMEM;
+    }
+    if ((!A.ctr && (hip_ok(hipMalloc((void**)&A.ctr, kAffCtrBytes)) || hip_ok(hipMemset(A.ctr, 0, kAffCtrBytes)))) ||
+        (!A.done && hip_ok(hipEventCreateWithFlags(&A.done, hipEventDisableTiming)))) {
+      (void)hipFree(A.tab);  // (the next batch starts over: a table is only ever used after its reset)
+      A.tab = nullptr;
+      return -GPC_EDEV;
+    }
+    A.seq = 0;
+  } else if (hip_ok(hipStreamWaitEvent(st, A.done, 0))) {
+    return -GPC_EDEV;
+  }
+  const Aff6Table t = aff6_table(ctx, D);
+  if (fresh) {
+    if (const int rc = launch_aff6_sweep(t, now, kAffSweepReset, st, nullptr)) {
+      (void)hipFree(A.tab);
+      A.tab = nullptr;
+      return rc;
+    }
+    A.swept = now;
+  } else if (A.seq >= 0xfffffffeu) {  // the sequence wraps: the bid words start over
+    if (const int rc = launch_aff6_sweep(t, now, kAffSweepBids, st, nullptr)) return rc;
+    A.seq = 0;
+  }
+  if (!fresh && now > A.swept) {
+    if (const int rc = launch_aff6_sweep(t, now, kAffSweepExpired, st, marks)) return rc;
+    A.swept = now;
+    A.sweeps++;
+  }
+  al->tab = t;
+  al->now = now;
+  al->seq = ++A.seq;
+  al->done = A.done;
+  return GPC_OK;
+}
+
+int gpc_affinity_stats6(gpc_ctx* ctx, uint32_t slot, gpc_affinity_counts* out) {
+  if (!ctx || !out || slot >= ctx->dev.size()) return -GPC_EINVAL;
+  *out = gpc_affinity_counts{};
+  if (!ctx->cfg.session_affinity6) return GPC_OK;
+  out->slots = uint64_t(1) << ctx->cfg.session_affinity6;
+  std::lock_guard<std::mutex> d(ctx->data);
+  DevState& D = ctx->dev[slot];
+  if (!D.a6.tab) return GPC_OK;
+  if (hip_ok(hipSetDevice(D.device)) || hip_ok(hipDeviceSynchronize())) return -GPC_EDEV;
+  unsigned long long c[kAffCounters] = {}, all[kAffCounterStripes][kAffCounters];
+  if (hip_ok(hipMemset2D(D.a6.ctr + kAffLive, kAffCounters * sizeof(unsigned long long), 0, sizeof(unsigned long long),
+                         kAffCounterStripes)))
+    return -GPC_EDEV;
+  if (const int rc = launch_aff6_sweep(aff6_table(ctx, D), aff_now(ctx), kAffSweepCount, nullptr, nullptr)) return rc;
+  if (hip_ok(hipDeviceSynchronize()) || hip_ok(hipMemcpy(all, D.a6.ctr, sizeof all, hipMemcpyDeviceToHost))) return -GPC_EDEV;
+  for (auto& stripe : all)
+    for (uint32_t k = 0; k < kAffCounters; k++) c[k] += stripe[k];
+  out->live = c[kAffLive];
+  out->learned = c[kAffLearned];
+  out->hits = c[kAffHits];
+  out->overflow = c[kAffOverflow];
+  out->sweeps = D.a6.sweeps;
+  return GPC_OK;
+}
+
+int gpc_debug_affinity_table6(gpc_ctx* ctx, uint32_t slot, gpc_affinity_entry6* buf, size_t cap, size_t* n) {
+  static_assert(sizeof(gpc_affinity_entry6) == 64, "gpc.py AFF_ENTRY6_DTYPE");
+  if (!ctx || !n || (!buf && cap) || slot >= ctx->dev.size()) return -GPC_EINVAL;
+  *n = 0;
+  std::lock_guard<std::mutex> g(ctx->ctl);  // (the Service flows name the entries' destinations)
+  std::vector<uint32_t> w;
+  uint32_t now = 0;
+  {
+    std::lock_guard<std::mutex> d(ctx->data);
+    DevState& D = ctx->dev[slot];
+    if (!ctx->cfg.session_affinity6 || !D.a6.tab) return GPC_OK;
+    now = aff_now(ctx);
+    w.resize(size_t(kAff6SlotWords) << ctx->cfg.session_affinity6);
+    if (hip_ok(hipSetDevice(D.device)) || hip_ok(hipDeviceSynchronize()) ||
+        hip_ok(hipMemcpy(w.data(), D.a6.tab, w.size() * 4, hipMemcpyDeviceToHost)))
+      return -GPC_EDEV;
+  }
+  auto bytes_of = [](const uint32_t* a, uint8_t* b) {
+    for (int k = 0; k < 16; k++) b[k] = uint8_t(a[k / 4] >> (24 - 8 * (k % 4)));
+  };
+  size_t k = 0;
+  for (size_t s = 0; s < w.size(); s += kAff6SlotWords) {
+    const uint32_t* q = w.data() + s;
+    if (!(q[0] | q[1]) || !q[15] || now >= q[13]) continue;
+    if (k < cap) {
+      gpc_affinity_entry6& e = buf[k];
+      e = gpc_affinity_entry6{};
+      e.install_id = q[15] >> 8;
+      e.endpoint_port = q[12];
+      e.expires = q[13];
+      bytes_of(q + 4, e.src);
+      bytes_of(q + 8, e.endpoint_ip);
+      (void)ctx->svc.affinity_dst6(q[15] >> 8, q[15] & 0xffu, e.dst);
+    }
+    k++;
+  }
+  *n = k;
+  return k > cap ? -GPC_ERANGE : GPC_OK;
+}
+
+int gpc_debug_set_affinity_seq6(gpc_ctx* ctx, uint32_t slot, uint32_t seq) {
+  if (!ctx || slot >= ctx->dev.size()) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> d(ctx->data);
+  DevState& D = ctx->dev[slot];
+  if (!ctx->cfg.session_affinity6 || !D.a6.tab) return -GPC_EINVAL;  // (a table's first use restarts the sequence)
+  D.a6.seq = seq;
+  return GPC_OK;
+}
+
+int gpc_debug_set_affinity6_digest_bits(gpc_ctx* ctx, uint32_t slot, uint32_t bits) {
+  if (!ctx || slot >= ctx->dev.size() || bits < 1 || bits > 64) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> d(ctx->data);
+  DevState& D = ctx->dev[slot];
+  if (!ctx->cfg.session_affinity6 || D.a6.tab) return -GPC_EINVAL;  // (claims of another width may be in the table)
+  D.aff6_bits = bits;
+  return GPC_OK;
+}
+
 int gpc_classify(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, int32_t count, void* stream) {
   return gpc_classify_on(ctx, 0, pk, n, out, nullptr, count, stream);
 }
@@ -1601,6 +1760,10 @@ int gpc_classify6_lb_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size
     shape.dest = pk->src6;
   }
   if (!svc6 && lb_out && n && hip_ok(hipMemsetAsync(lb_out, 0, n * sizeof(gpc_lb_result6), st))) return -GPC_EDEV;
+  // Session affinity: the bound IPv6 Service image holds an affinity Service and the context has an
+  // IPv6 table. The learn and resolve passes then take v6_lb_kernel's place (same scratch columns);
+  // any other batch takes exactly the launches it took before.
+  const bool affinity6 = n && svc6 && D.cur.svc6->affinity && ctx->cfg.session_affinity6;
   uint8_t* scratch = nullptr;
   if (n && ctx->group_v6 && group_batch(ctx, n, *D.cur.v6, D.cur.v6_jhdr != 0)) {
     if (const int e = group_scratch_for(ctx, D, st, code_bytes + group_scratch_bytes(shape, n, false), &scratch)) return e;
@@ -1608,9 +1771,14 @@ int gpc_classify6_lb_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size
   }
   if (n && !scratch)
     if (const int e = group_scratch(D, st, code_bytes, &scratch)) return e;
+  LaunchMarks* const marks = n ? next_marks(D) : nullptr;
+  Aff6Launch al{};
+  if (affinity6)
+    if (const int e = aff6_prepare(ctx, D, st, marks, &al)) return e;
   int rc = launch_classify6(ep, *pk, n, out, D.d_counters, count, ga.scratch ? &ga : nullptr,
-                            reinterpret_cast<uint32_t*>(scratch), st, n ? next_marks(D) : nullptr, svc6,
-                            svc6 && scratch ? scratch + code_words : nullptr, reinterpret_cast<uint4*>(lb_out));
+                            reinterpret_cast<uint32_t*>(scratch), st, marks, svc6,
+                            svc6 && scratch ? scratch + code_words : nullptr, reinterpret_cast<uint4*>(lb_out),
+                            affinity6 ? &al : nullptr);
   if (!rc && scratch) rc = group_scratch_used(D, st);
   if (rc || n == 0) return rc;
   pace.record();
@@ -1878,7 +2046,8 @@ int gpc_launch_times(gpc_ctx* ctx, gpc_launch_time* out, size_t cap, size_t* n) 
   if (!ctx || !n || (!out && cap)) return -GPC_EINVAL;
   static const char* const names[kLaunchKinds] = {"group_tiles", "classify_egress", "classify_ingress", "classify_both",
                                                   "unpermute",   "v6_codes",        "v6_lb",            "aff_learn",
-                                                  "aff_resolve", "aff_sweep"};
+                                                  "aff_resolve", "aff_sweep",       "aff6_learn",       "aff6_resolve",
+                                                  "aff6_sweep"};
   double ms[kLaunchKinds] = {};
   uint32_t cnt[kLaunchKinds] = {};
   size_t dropped = 0;
@@ -2304,6 +2473,7 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
     else if (!ctx->svc_blob.empty() && (rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc))) return fail(rc);
     if (svc_changed && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
     if (svc_changed && !ctx->svc6_blob.empty() && (rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6))) return fail(rc);
+    if (svc_changed && ne[k].svc6) ne[k].svc6->affinity = svc_has_affinity(ctx->svc6_blob);
     ne[k].epoch = epoch;
     // counters: grow to the slot count, zero released slots (their Metric flows were deleted)
     nc[k] = D.d_counters;

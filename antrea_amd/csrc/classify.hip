@@ -923,10 +923,13 @@ uint64_t v6_lb_scratch_bytes(uint64_t n) {  // dst6 dport out_port svc_group des
   return (16 + 2 + 4 + 4 + 1) * n + 5 * 256;
 }
 
+static int launch_aff6(const V6LbArgs& v, const gpc_pkt_soa& pk, uint64_t n, const Aff6Launch& al, hipStream_t stream, LaunchMarks* marks);
+
 int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out,
                      unsigned long long* counters, int count, const GroupArgs* group, uint32_t* codes, hipStream_t stream,
-                     LaunchMarks* marks, const uint32_t* svc6, uint8_t* lb_scratch, uint4* lb_out6) {
+                     LaunchMarks* marks, const uint32_t* svc6, uint8_t* lb_scratch, uint4* lb_out6, const Aff6Launch* al) {
   if (n == 0) return 0;
+  if (al && (!svc6 || !al->tab.w)) return -GPC_EINVAL;
   if (n > kMaxPackets || !codes || (svc6 && !lb_scratch)) return -GPC_EINVAL;
   V6Cols cols{{pk.src6, pk.dst6, nullptr, nullptr}};
   uint32_t nc = 2;
@@ -959,8 +962,12 @@ int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc
     a.dport_out = reinterpret_cast<uint16_t*>(take(2 * n));
     a.dest_out = take(n);
     a.lb_out = lb_out6;
-    launch_mark(marks, kLaunchV6Lb, stream);
-    hipLaunchKernelGGL(v6_lb_kernel, dim3(uint32_t((n + kLbBlock - 1) / kLbBlock)), dim3(kLbBlock), 0, stream, a, n);
+    if (al) {  // session affinity: the learn and resolve passes write what v6_lb_kernel would
+      if (const int rc = launch_aff6(a, pk, n, *al, stream, marks)) return rc;
+    } else {
+      launch_mark(marks, kLaunchV6Lb, stream);
+      hipLaunchKernelGGL(v6_lb_kernel, dim3(uint32_t((n + kLbBlock - 1) / kLbBlock)), dim3(kLbBlock), 0, stream, a, n);
+    }
     cols.c[1] = reinterpret_cast<const uint8_t*>(a.dst_out);
     p4.dport = a.dport_out;
     p4.out_port = a.out_port_out;
@@ -1164,6 +1171,100 @@ int launch_classify_aff(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, 
   EpochArgs e = ep;
   e.svc = nullptr;
   return launch_classify(e, p4, n, out, nullptr, counters, count, group, stream, marks, nullptr, true);
+}
+
+// Session affinity of IPv6 Services (core.hpp "IPv6 affinity table"): for a batch against an IPv6
+// Service image with affinity Services, aff6_learn_kernel and aff6_resolve_kernel take the place of
+// v6_lb_kernel (aff6_sweep_kernel in front when the clock moved) and write the same scratch columns;
+// the code pass and the policy launches follow unchanged. One packet (one slot in the sweep) per
+// lane, 256-thread blocks, the tail bounds-checked, no LDS; no lane waits for another.
+struct Aff6Args {
+  const uint32_t* svc;  // IPv6 Service image with affinity Services
+  Aff6Table tab;
+  uint32_t now, seq;
+  Aff6Cols pk;
+  const uint32_t *out_port, *svc_group;  // svc_group, dest: optional
+  const uint8_t* dest;
+  uint4* dst_out;
+  uint16_t* dport_out;
+  uint32_t *out_port_out, *svc_group_out;
+  uint8_t* dest_out;
+  uint4* lb_out;  // two per packet; may be null
+};
+__device__ __forceinline__ Aff6Table aff6_striped(Aff6Table t) {
+  t.ctr += (blockIdx.x % kAffCounterStripes) * kAffCounters;
+  return t;
+}
+__global__ __launch_bounds__(kLbBlock) void aff6_sweep_kernel(Aff6Table t, uint32_t now, uint32_t mode) {
+  t = aff6_striped(t);
+  const uint64_t s = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
+  if (s < (uint64_t(1) << t.log2)) aff6_sweep_slot<AffOpsDev>(t, uint32_t(s), now, mode);
+}
+__global__ __launch_bounds__(kLbBlock) void aff6_learn_kernel(Aff6Args a, uint64_t n) {
+  const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
+  if (i >= n) return;
+  a.tab = aff6_striped(a.tab);
+  aff6_learn<AffOpsDev>(a.svc, a.tab, a.now, a.seq, uint32_t(i), a.pk);
+}
+__global__ __launch_bounds__(kLbBlock) void aff6_resolve_kernel(Aff6Args a, uint64_t n) {
+  const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
+  if (i >= n) return;
+  a.tab = aff6_striped(a.tab);
+  uint32_t dst[4];
+  aff6_addr(a.pk.dst6, i, dst);
+  uint32_t dport = a.pk.dport[i];
+  uint32_t out_port = a.out_port[i];
+  uint32_t svc_group = a.svc_group ? a.svc_group[i] : 0u;
+  uint32_t dest = a.dest ? a.dest[i] : 0u;
+  uint32_t lb[8];
+  bool collided;
+  const uint32_t f = lb_stage6_aff(a.svc, a.tab, a.now, a.seq, uint32_t(i), a.pk, dst, dport, a.pk.proto[i], svc_group, out_port,
+                                   dest, lb, &collided);
+  AffOpsDev::count(a.tab.ctr + kAffLearned, (f & GPC_LB_LEARNED) != 0u);
+  AffOpsDev::count(a.tab.ctr + kAffHits, (f & (GPC_LB_AFFINITY | GPC_LB_LEARNED)) == GPC_LB_AFFINITY);
+  AffOpsDev::count(a.tab.ctr + kAffOverflow, collided);
+  a.dst_out[i] = make_uint4(__builtin_bswap32(dst[0]), __builtin_bswap32(dst[1]), __builtin_bswap32(dst[2]), __builtin_bswap32(dst[3]));
+  a.dport_out[i] = uint16_t(dport);
+  a.out_port_out[i] = out_port;
+  a.svc_group_out[i] = svc_group;
+  a.dest_out[i] = uint8_t((dest & ~kDestNoEndpoint) | ((f & GPC_LB_NO_ENDPOINT) ? kDestNoEndpoint : 0u));
+  if (a.lb_out) {
+    a.lb_out[2 * i] = make_uint4(__builtin_bswap32(lb[0]), __builtin_bswap32(lb[1]), __builtin_bswap32(lb[2]), __builtin_bswap32(lb[3]));
+    a.lb_out[2 * i + 1] = make_uint4(lb[4], lb[5], lb[6], 0u);
+  }
+}
+
+static int launch_aff6(const V6LbArgs& v, const gpc_pkt_soa& pk, uint64_t n, const Aff6Launch& al, hipStream_t stream, LaunchMarks* marks) {
+  Aff6Args a{};
+  a.svc = v.svc;
+  a.tab = al.tab;
+  a.now = al.now;
+  a.seq = al.seq;
+  a.pk = Aff6Cols{pk.src6, pk.dst6, pk.sport, pk.dport, pk.proto, pk.ct_state, n};
+  a.out_port = v.out_port;
+  a.svc_group = v.svc_group;
+  a.dest = v.dest;
+  a.dst_out = v.dst_out;
+  a.dport_out = v.dport_out;
+  a.out_port_out = v.out_port_out;
+  a.svc_group_out = v.svc_group_out;
+  a.dest_out = v.dest_out;
+  a.lb_out = v.lb_out;
+  const dim3 grid(uint32_t((n + kLbBlock - 1) / kLbBlock));
+  launch_mark(marks, kLaunchAff6Learn, stream);
+  hipLaunchKernelGGL(aff6_learn_kernel, grid, dim3(kLbBlock), 0, stream, a, n);
+  launch_mark(marks, kLaunchAff6Resolve, stream);
+  hipLaunchKernelGGL(aff6_resolve_kernel, grid, dim3(kLbBlock), 0, stream, a, n);
+  // the table is free for the next affinity batch of the slot from here on
+  if (al.done && hipEventRecord(al.done, stream) != hipSuccess) return -GPC_EDEV;
+  return hipGetLastError() == hipSuccess ? 0 : -GPC_EDEV;
+}
+
+int launch_aff6_sweep(const Aff6Table& t, uint32_t now, uint32_t mode, hipStream_t stream, LaunchMarks* marks) {
+  launch_mark(marks, kLaunchAff6Sweep, stream);
+  const uint64_t slots = uint64_t(1) << t.log2;
+  hipLaunchKernelGGL(aff6_sweep_kernel, dim3(uint32_t((slots + kLbBlock - 1) / kLbBlock)), dim3(kLbBlock), 0, stream, t, now, mode);
+  return hipGetLastError() == hipSuccess ? 0 : -GPC_EDEV;
 }
 
 #if defined(GPC_STAMPS)

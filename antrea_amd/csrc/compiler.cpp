@@ -229,15 +229,19 @@ std::string Action::str() const {  // utils.go:600-760 (the subset NP flows use)
       std::snprintf(buf, sizeof buf, "ct(commit,table=%s,zone=%u,exec(set_field:0x20/0x20->ct_mark,set_field:0x40/0x40->ct_mark))",
                     table_name(uint8_t(a)), b);
       return buf;
-    case ACT_LEARN: {  // nxActionLearnToString as client_test.go prints serviceLearnFlow (IPv4)
+    case ACT_LEARN: {  // nxActionLearnToString as client_test.go prints serviceLearnFlow (c & 2: IPv6)
       const char* const dst = b == 6 ? "TCP" : b == 17 ? "UDP" : "SCTP";
+      const bool v6 = (c & 2u) != 0;
       char lbuf[640];
       std::snprintf(lbuf, sizeof lbuf,
-                    "learn(table=SessionAffinity,hard_timeout=%u,priority=200,delete_learned,cookie=0x%llx,eth_type=0x800,"
-                    "nw_proto=0x%x,OXM_OF_%s_DST[],NXM_OF_IP_DST[],NXM_OF_IP_SRC[],load:NXM_NX_REG4[0..15]->NXM_NX_REG4[0..15],"
-                    "load:NXM_NX_REG4[26]->NXM_NX_REG4[26],load:NXM_NX_REG3[]->NXM_NX_REG3[],load:0x2->NXM_NX_REG4[16..18],"
+                    "learn(table=SessionAffinity,hard_timeout=%u,priority=200,delete_learned,cookie=0x%llx,eth_type=0x%s,"
+                    "nw_proto=0x%x,OXM_OF_%s_DST[],%s,load:NXM_NX_REG4[0..15]->NXM_NX_REG4[0..15],"
+                    "load:NXM_NX_REG4[26]->NXM_NX_REG4[26],load:%s,load:0x2->NXM_NX_REG4[16..18],"
                     "load:0x1->NXM_NX_REG0[9]%s)",
-                    a, (unsigned long long)lv, b, dst, c ? ",load:0x1->NXM_NX_REG4[21]" : "");
+                    a, (unsigned long long)lv, v6 ? "86dd" : "800", b, dst,
+                    v6 ? "NXM_NX_IPV6_DST[],NXM_NX_IPV6_SRC[]" : "NXM_OF_IP_DST[],NXM_OF_IP_SRC[]",
+                    v6 ? "NXM_NX_XXREG3[]->NXM_NX_XXREG3[]" : "NXM_NX_REG3[]->NXM_NX_REG3[]",
+                    (c & 1u) ? ",load:0x1->NXM_NX_REG4[21]" : "");
       return lbuf;
     }
     case ACT_RESUBMIT: return std::string("resubmit:") + table_name(uint8_t(a));

@@ -2562,6 +2562,237 @@ GPC_HD uint32_t lb_stage6(const uint32_t* sv, SrcFn src, uint32_t* dst, uint32_t
   return flags;
 }
 
+// ------------------------------------------------------------------------- IPv6 affinity table
+// sessionAffinity: ClientIP of IPv6 Services (gpc_config.session_affinity6): the protocol of the
+// "Affinity table" above over a key that no single compare-and-swap can hold -- (install id,
+// NodePort address id, 128-bit client address). Claim by digest, verify by key:
+//   2^log2 slots of 64 B (one line each), 16 words:
+//     [0..1]  claim word: a non-zero 64-bit digest of the key, ANDed with the table's mask (all ones;
+//             a test hook narrows it so that digests collide). 0 = empty slot. The four candidate
+//             slots derive from the digest as aff_candidates derives them from the IPv4 key.
+//     [2..3]  bid word, as in the IPv4 table
+//     [4..7]  client address, host-order words    [8..11] Endpoint address
+//     [12]    port | (GPC_LB_REMOTE bit) << 16    [13] expires    [14] Endpoint index hint
+//     [15]    install id << 8 | NodePort address id (never 0 once written: install ids start at 1)
+//   Words 4..15 are written only by the winner of a bid, in a resolve pass, and cleared only by a
+//   sweep: inside a learn pass they are stable -- all zero (the slot was claimed in this pass) or what
+//   an earlier batch wrote. A packet that finds its digest in a slot written with another key (a
+//   digest collision with an entry) does not bid. Two keys with one digest that claim a slot in the
+//   same learn pass both bid; in the resolve pass every packet compares the key of the bid's winner
+//   (its columns at the winner's index) with its own, and only the winner's key is learned. The
+//   colliding packets take their own hash choice and are counted in ctr[kAffOverflow] (once per +new
+//   packet, in the resolve pass; the learn pass counts the packets whose digest found no slot). So
+//   two different keys never share an entry, no lane waits for another, and ownership is decided
+//   only from what the atomics return.
+struct Aff6Table {
+  uint32_t* w;              // slots: 16 words each
+  uint32_t log2;            // 2^log2 slots, log2 >= 2
+  unsigned long long* ctr;  // AffCounter array (device: kAffCounterStripes copies)
+  uint64_t mask;            // digest mask
+};
+constexpr uint32_t kAff6SlotWords = 16;
+// The batch columns the passes read beside the packet's own: the resolve pass loads the winner's.
+struct Aff6Cols {
+  const uint8_t *src6, *dst6;  // 16 network-order bytes per packet, 16-B aligned
+  const uint16_t *sport, *dport;
+  const uint8_t *proto, *ct_state;  // ct_state: optional
+  uint64_t n;                       // packets of the batch
+};
+GPC_HD void aff6_addr(const uint8_t* col, uint64_t i, uint32_t* a) {  // one 128-bit load
+#if defined(__HIPCC__)
+  const uint4 v = reinterpret_cast<const uint4*>(col)[i];
+  a[0] = __builtin_bswap32(v.x), a[1] = __builtin_bswap32(v.y), a[2] = __builtin_bswap32(v.z), a[3] = __builtin_bswap32(v.w);
+#else
+  v6_words(col + 16 * i, a);
+#endif
+}
+GPC_HD bool aff6_same(const uint32_t* a, const uint32_t* b) { return a[0] == b[0] && a[1] == b[1] && a[2] == b[2] && a[3] == b[3]; }
+GPC_HD uint64_t aff6_digest(uint32_t id, const uint32_t* a, uint64_t mask) {
+  const uint64_t hi = (uint64_t(a[0]) << 32) | a[1], lo = (uint64_t(a[2]) << 32) | a[3];
+  const uint64_t d = mix64(hi ^ mix64(lo ^ mix64(uint64_t(id) ^ 0x5851f42d4c957f2dull))) & mask;
+  return d ? d : 1ull;
+}
+GPC_HD uint64_t* aff6_claim_word(const Aff6Table& t, uint32_t slot) { return reinterpret_cast<uint64_t*>(t.w + size_t(slot) * kAff6SlotWords); }
+GPC_HD uint64_t* aff6_bid_word(const Aff6Table& t, uint32_t slot) { return aff6_claim_word(t, slot) + 1; }
+GPC_HD uint32_t* aff6_body(const Aff6Table& t, uint32_t slot) { return t.w + size_t(slot) * kAff6SlotWords + 4; }  // words 4..15
+GPC_HD uint32_t aff6_find(const Aff6Table& t, uint64_t digest, const uint32_t* c) {
+  uint32_t r = kAffNone;
+#pragma unroll
+  for (int k = 3; k >= 0; k--) r = *aff6_claim_word(t, c[k]) == digest ? c[k] : r;
+  return r;
+}
+// The Service a packet addresses, as lb_stage6 finds it (aff_svc_lookup over 128-bit addresses).
+GPC_HD uint32_t aff6_svc_lookup(const uint32_t* sv, uint32_t proto, const uint32_t* dst, uint32_t dport, uint32_t& np_id) {
+  const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+  np_id = 0;
+  uint32_t si = svc6_lookup(sv, proto, dst, dport);
+  if (si == 0xffffffffu && h->n_np) {
+    uint32_t at = kAffNone;
+    for (uint32_t i = 0; i < h->n_np; i++) at = aff6_same(sv + h->np_off + 4 * i, dst) ? i : at;
+    if (at != kAffNone) {
+      const uint32_t zero[4] = {0u, 0u, 0u, 0u};
+      si = svc6_lookup(sv, proto, zero, dport);
+      if (h->n_aff) np_id = sv[h->aff_off + h->n_svc + at];
+    }
+  }
+  return si;
+}
+// Index (within the Service) of the Endpoint (address, port) in the bound image, or kAffNone.
+GPC_HD uint32_t aff6_find_endpoint(const uint32_t* sv, const uint32_t* s, const uint32_t* ip, uint32_t port, uint32_t hint) {
+  const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+  const uint32_t n = s[1] & 0xffffffu;
+  const uint32_t* e = sv + h->ep_off + kSvc6EpWords * size_t(s[0]);
+  if (hint < n && aff6_same(e + kSvc6EpWords * hint, ip) && (e[kSvc6EpWords * hint + 4] & 0xffffu) == port) return hint;
+  for (uint32_t i = 0; i < n; i++)
+    if (aff6_same(e + kSvc6EpWords * i, ip) && (e[kSvc6EpWords * i + 4] & 0xffffu) == port) return i;
+  return kAffNone;
+}
+// b: words 4..15 of a slot written with the packet's key
+GPC_HD bool aff6_entry_valid(const uint32_t* sv, const uint32_t* s, const uint32_t* b, uint32_t now, uint32_t* index) {
+  if (now >= b[9]) return false;  // hard timeout: live while now < expires
+  *index = aff6_find_endpoint(sv, s, b + 4, b[8] & 0xffffu, b[10]);
+  return *index != kAffNone;
+}
+
+// One slot of the sweep pass: the modes of aff_sweep_slot.
+template <class Ops>
+GPC_HD void aff6_sweep_slot(const Aff6Table& t, uint32_t slot, uint32_t now, uint32_t mode) {
+  uint64_t* const claim = aff6_claim_word(t, slot);
+  uint32_t* const b = aff6_body(t, slot);
+  if (mode == kAffSweepCount) {
+    Ops::count(t.ctr + kAffLive, *claim != 0 && b[11] != 0 && now < b[9]);
+    return;
+  }
+  if (mode == kAffSweepReset || mode == kAffSweepBids) *aff6_bid_word(t, slot) = ~0ull;
+  if (mode == kAffSweepReset || (mode == kAffSweepExpired && *claim != 0 && now >= b[9])) {
+    *claim = 0;
+    for (int k = 0; k < 12; k++) b[k] = 0;
+  }
+}
+
+// The learn pass of packet i (caller index). Counts the packet in ctr[kAffOverflow] when its digest
+// found no slot.
+template <class Ops>
+GPC_HD void aff6_learn(const uint32_t* sv, const Aff6Table& t, uint32_t now, uint32_t seq, uint32_t i, const Aff6Cols& pk) {
+  bool overflow = false;
+  const uint32_t proto = pk.proto[i], ct_state = pk.ct_state ? pk.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK);
+  if ((ct_state & GPC_CT_NEW) && (proto == 6 || proto == 17 || proto == 132)) {
+    const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+    uint32_t dst[4], np_id;
+    aff6_addr(pk.dst6, i, dst);
+    const uint32_t si = aff6_svc_lookup(sv, proto, dst, pk.dport[i], np_id);
+    const uint32_t* s = sv + h->svc_off + 4 * size_t(si == kAffNone ? 0u : si);
+    if (si != kAffNone && (s[3] & kSvcAffinity) && (s[1] & 0xffffffu)) {
+      uint32_t src[4], c[4];
+      aff6_addr(pk.src6, i, src);
+      const uint32_t id = (sv[h->aff_off + si] << 8) | (np_id & 0xffu);
+      const uint64_t digest = aff6_digest(id, src, t.mask);
+      aff_candidates(digest, t.log2, c);
+      uint32_t slot = aff6_find(t, digest, c);
+      for (int k = 0; k < 4 && slot == kAffNone; k++) {  // find or claim, in the fixed order
+        const uint64_t old = Ops::cas(aff6_claim_word(t, c[k]), 0ull, digest);
+        if (old == 0ull || old == digest) slot = c[k];
+      }
+      overflow = slot == kAffNone;
+      if (slot != kAffNone) {
+        // stable in this pass: zero (claimed in it) or the key an earlier batch wrote
+        const uint32_t* b = aff6_body(t, slot);
+        const bool written = b[11] != 0u, mine = b[11] == id && aff6_same(b, src);
+        uint32_t index;
+        const bool settled = written && mine && aff6_entry_valid(sv, s, b, now, &index);
+        // (written with another key: a digest collision with an entry -- no bid; the resolve pass counts it)
+        if (!settled && (!written || mine)) Ops::min(aff6_bid_word(t, slot), (uint64_t(~seq) << 32) | i);
+      }
+    }
+  }
+  Ops::count(t.ctr + kAffOverflow, overflow);
+}
+
+// lb_stage6 with the affinity branch (the resolve pass) of packet i: dst / dport are the packet's
+// own (rewritten by the DNAT), the winner's columns are read from pk. Returns the GPC_LB_* flags;
+// *collided: a +new packet whose key met another key's digest (counted by the caller).
+GPC_HD uint32_t lb_stage6_aff(const uint32_t* sv, const Aff6Table& t, uint32_t now, uint32_t seq, uint32_t i, const Aff6Cols& pk,
+                              uint32_t* dst, uint32_t& dport, uint32_t proto, uint32_t& svc_group, uint32_t& out_port,
+                              uint32_t& dest, uint32_t* o, bool* collided) {
+  for (int k = 0; k < 8; k++) o[k] = 0;
+  *collided = false;
+  if (proto != 6 && proto != 17 && proto != 132) return 0;
+  const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
+  uint32_t np_id;
+  const uint32_t si = aff6_svc_lookup(sv, proto, dst, dport, np_id);
+  if (si == kAffNone) return 0;
+  const uint32_t* s = sv + h->svc_off + 4 * size_t(si);
+  const uint32_t n = s[1] & 0xffffffu, lg = s[1] >> 24;
+  uint32_t flags = GPC_LB_HIT;
+  o[5] = s[2];
+  if (s[3] & kSvcLoadReg7) svc_group = s[2];
+  if (n == 0) {
+    flags |= GPC_LB_NO_ENDPOINT;
+    o[4] = flags << 16;
+    return flags;
+  }
+  uint32_t src[4];
+  aff6_addr(pk.src6, i, src);
+  uint32_t index = kAffNone, pick_sport = pk.sport[i], slot = kAffNone, id = 0;
+  if (s[3] & kSvcAffinity) {
+    id = (sv[h->aff_off + si] << 8) | (np_id & 0xffu);
+    const uint64_t digest = aff6_digest(id, src, t.mask);
+    uint32_t c[4];
+    aff_candidates(digest, t.log2, c);
+    slot = aff6_find(t, digest, c);
+    if (slot != kAffNone) {
+      const uint32_t ct_state = pk.ct_state ? pk.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK);
+      const uint64_t bid = *aff6_bid_word(t, slot);
+      if (uint32_t(bid >> 32) == ~seq && uint32_t(bid) < pk.n) {  // a bid of this launch: winner = its low half
+        const uint32_t w = uint32_t(bid);
+        // the winner's key is this packet's when client, destination, port and protocol agree
+        uint32_t ws[4], wd[4];
+        aff6_addr(pk.src6, w, ws);
+        aff6_addr(pk.dst6, w, wd);
+        if (aff6_same(ws, src) && aff6_same(wd, dst) && pk.dport[w] == dport && pk.proto[w] == proto) {
+          if (w <= i) {
+            pick_sport = pk.sport[w];
+            flags |= GPC_LB_AFFINITY | (w == i ? uint32_t(GPC_LB_LEARNED) : 0u);
+          }
+        } else {
+          *collided = (ct_state & GPC_CT_NEW) != 0u;  // another key's digest won the slot in this pass
+        }
+      } else {
+        const uint32_t* b = aff6_body(t, slot);
+        if (b[11] == id && aff6_same(b, src)) {
+          if (aff6_entry_valid(sv, s, b, now, &index)) flags |= GPC_LB_AFFINITY;
+          else index = kAffNone;
+        } else {
+          *collided = (ct_state & GPC_CT_NEW) != 0u && b[11] != 0u;  // the slot holds another key's entry
+        }
+      }
+    }
+  }
+  const uint32_t fdst = fold6(dst);  // the pre-NAT destination
+  if (index == kAffNone) index = (lb_hash(fold6(src), fdst, pick_sport, dport, proto) & ((1u << lg) - 1u)) % n;
+  const uint32_t* e = sv + h->ep_off + kSvc6EpWords * (size_t(s[0]) + index);
+  if (flags & GPC_LB_LEARNED) {  // the winner: no other lane reads or writes these words in this pass
+    uint32_t* b = aff6_body(t, slot);
+    b[0] = src[0], b[1] = src[1], b[2] = src[2], b[3] = src[3];
+    b[4] = e[0], b[5] = e[1], b[6] = e[2], b[7] = e[3];
+    b[8] = (e[4] & 0xffffu) | (((e[4] >> 16) & GPC_LB_REMOTE) << 16);
+    b[9] = now + (s[3] >> 16);
+    b[10] = index;
+    b[11] = id;
+  }
+  flags |= e[4] >> 16;
+  o[0] = e[0], o[1] = e[1], o[2] = e[2], o[3] = e[3];
+  o[4] = (e[4] & 0xffffu) | (flags << 16);
+  o[6] = e[5];
+  if (flags & GPC_LB_DNAT) {
+    dst[0] = e[0], dst[1] = e[1], dst[2] = e[2], dst[3] = e[3];
+    dport = e[4] & 0xffffu;
+  }
+  out_port = e[5];
+  dest = e[6];
+  return flags;
+}
+
 // Verdict word layout (gpc_verdict): conj_id | action | table | tier | flags.
 struct VerdictOut {
   uint32_t conj;

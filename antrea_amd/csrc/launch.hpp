@@ -47,14 +47,14 @@ uint64_t group_scratch_bytes(const gpc_pkt_soa& pk, uint64_t n, bool lb);
 // Launch timing (gpc_set_launch_timing): an event is recorded on the launch stream before every
 // kernel of one gpc_classify* call and after the last, named by the kernel that follows it.
 struct LaunchMarks {
-  static constexpr int kMax = 8;
+  static constexpr int kMax = 12;
   hipEvent_t ev[kMax];
   uint8_t kind[kMax];  // LaunchKind of the kernel starting at ev[i] (kLaunchEnd: the closing event)
   int n;
 };
 enum LaunchKind : uint8_t {
   kLaunchGroup, kLaunchEgress, kLaunchIngress, kLaunchBoth, kLaunchUnpermute, kLaunchCodes, kLaunchV6Lb, kLaunchAffLearn, kLaunchAffResolve,
-  kLaunchAffSweep, kLaunchKinds, kLaunchEnd
+  kLaunchAffSweep, kLaunchAff6Learn, kLaunchAff6Resolve, kLaunchAff6Sweep, kLaunchKinds, kLaunchEnd
 };
 inline void launch_mark(LaunchMarks* m, uint8_t kind, hipStream_t s) {
   if (!m || m->n >= LaunchMarks::kMax) return;
@@ -74,12 +74,22 @@ int launch_classify(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_
 // rewrites into lb_scratch (v6_lb_scratch_bytes(n) bytes) and the optional LB results (two uint4 per
 // packet, gpc_lb_result6) to lb_out6; the code pass then codes {src6, post-DNAT dst6, ct_src6?,
 // ct_dst6 or the original dst6}, and the policy launches run as `resolved` over those columns.
+// al: svc6 holds session-affinity Services and the slot has an IPv6 affinity table (core.hpp "IPv6
+// affinity table"): aff6_learn_kernel and aff6_resolve_kernel run in place of v6_lb_kernel and write
+// the same columns; al->done is recorded after them (the next such batch of the slot waits for it).
+struct Aff6Launch {
+  Aff6Table tab;
+  uint32_t now, seq;
+  hipEvent_t done;
+};
 uint32_t v6_code_columns(const gpc_pkt_soa& pk, bool svc = false);
 uint64_t v6_lb_scratch_bytes(uint64_t n);
 int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out,
                      unsigned long long* counters, int count, const GroupArgs* group, uint32_t* codes, hipStream_t stream,
                      LaunchMarks* marks = nullptr, const uint32_t* svc6 = nullptr, uint8_t* lb_scratch = nullptr,
-                     uint4* lb_out6 = nullptr);
+                     uint4* lb_out6 = nullptr, const Aff6Launch* al = nullptr);
+// One pass over the IPv6 affinity table's slots (core.hpp aff6_sweep_slot modes).
+int launch_aff6_sweep(const Aff6Table& t, uint32_t now, uint32_t mode, hipStream_t stream, LaunchMarks* marks = nullptr);
 // IPv4 batch against a Service image with session-affinity Services (ep.svc) and the slot's affinity
 // table (core.hpp "Affinity table"): aff_learn_kernel and aff_resolve_kernel run the Service stage
 // with the learned flows and write the columns it rewrites into lb_scratch

@@ -123,7 +123,7 @@ enum ActKind : uint8_t {
   ACT_SET_XXREG3,  // set_field:0x<lv lm>->xxreg3 (IPv6 group buckets)
   ACT_CT_DNAT6,    // ACT_CT_DNAT with nat(dst=[lv lm]:c)
   ACT_LEARN        // learn(table=SessionAffinity,hard_timeout=a,...): serviceLearnFlow (pipeline.go:2316-2371);
-                   // b = IP protocol, c != 0: loads ToExternalAddressRegMark, lv = cookie (IPv4 Services)
+                   // b = IP protocol, c & 1: loads ToExternalAddressRegMark, c & 2: an IPv6 Service, lv = cookie
 };
 
 struct Action {

@@ -4,8 +4,10 @@
 // Endpoint is loaded into / matched in xxreg3, its flows are tcp6 / udp6 / sctp6 with zone 65510.
 #include "service.hpp"
 
+#include <array>
 #include <cstdio>
 #include <cstring>
+#include <tuple>
 
 #include "core.hpp"
 
@@ -225,8 +227,8 @@ int FeatureService::install_service_flows(const gpc_service_config& c) {
   if (!ip_proto(c.protocol) || !family_ok(c.family)) return -GPC_EINVAL;
   if (c.is_dsr || c.is_nested || (c.is_external && c.traffic_policy_local))
     return -GPC_EINVAL;  // DSR / multi-cluster / short-circuit flows: not modelled
-  // learn flows: IPv4 Services of a context with an affinity table
-  if (c.affinity_timeout && (!cfg_.session_affinity || c.family != 4)) return -GPC_EINVAL;
+  // learn flows: Services of a context with an affinity table for their family
+  if (c.affinity_timeout && !(c.family == 6 ? cfg_.session_affinity6 : cfg_.session_affinity)) return -GPC_EINVAL;
   if (c.affinity_timeout && next_install_ >= kMaxInstallId) return -GPC_ENOMEM;
   const IPAddr ip = to_ip(c.ip, c.family);
   const uint32_t gid = c.traffic_policy_local ? c.local_group_id : c.cluster_group_id;  // TrafficPolicyGroupID
@@ -272,7 +274,7 @@ int FeatureService::install_service_flows(const gpc_service_config& c) {
     Action learn{ACT_LEARN};
     learn.a = c.affinity_timeout;
     learn.b = ip_proto(c.protocol);
-    learn.c = c.is_external;
+    learn.c = (c.is_external ? 1u : 0u) | (c.family == 6 ? 2u : 0u);
     learn.lv = l.cookie;
     learn.lm = ++next_install_;  // the install id of its learned flows
     Action nx{ACT_GOTO};
@@ -319,6 +321,16 @@ int FeatureService::set_node_port_addresses(const uint8_t* ips, uint8_t family, 
     if (family == 6) std::memcpy(v, kVirtualNodePortDNAT6, 16);
     else for (int k = 0; k < 4; k++) v[k] = uint8_t(kVirtualNodePortDNAT >> (24 - 8 * k));
     addrs.push_back(to_ip(v, family));
+  }
+  if (family == 6 && cfg_.session_affinity6) {  // the same for the IPv6 addresses, ids of their own
+    size_t fresh = 0;
+    for (const IPAddr& a : addrs) fresh += !np_ids6_.count(a);
+    if (np_ids6_.size() + fresh > kMaxNodePortId) return -GPC_EINVAL;
+    for (const IPAddr& a : addrs)
+      if (!np_ids6_.count(a)) {
+        const uint32_t id = uint32_t(np_ids6_.size()) + 1;
+        np_ids6_[a] = id;
+      }
   }
   if (family == 4 && cfg_.session_affinity) {  // ids of the addresses, as the learned flows of NodePort Services key them
     size_t fresh = 0;
@@ -371,6 +383,24 @@ uint32_t FeatureService::affinity_dst(uint32_t install, uint32_t np_id) const {
         if (np.second == np_id) return np.first;
     }
   return 0;
+}
+
+bool FeatureService::affinity_dst6(uint32_t install, uint32_t np_id, uint8_t* out) const {
+  for (auto& kv : cached_)
+    for (auto& f : kv.second) {
+      if (f.acts.empty() || f.acts[0].kind != ACT_LEARN || f.acts[0].lm != install || f.m.dl_type != kEthIPv6) continue;
+      if (f.m.nw_dst.set) {
+        std::memcpy(out, f.m.nw_dst.addr.b, 16);
+        return true;
+      }
+      for (auto& np : np_ids6_)
+        if (np.second == np_id) {
+          std::memcpy(out, np.first.b, 16);
+          return true;
+        }
+    }
+  std::memset(out, 0, 16);
+  return false;
 }
 
 std::string FeatureService::dump_flows() const {
@@ -658,7 +688,13 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
     uint32_t a[4];
     uint32_t gid;
     bool reg7;
+    bool aff;  // the ServiceLB flow loads EpToLearnRegMark: its learn flow follows the group
   };
+  struct Learn {
+    uint32_t timeout, install;
+  };
+  typedef std::tuple<uint8_t, uint16_t, std::array<uint32_t, 4>> SvcKey;  // (protocol, port, address; 0: NodePort)
+  std::map<SvcKey, Learn> learn;  // serviceLearnFlow per Service key
   std::vector<Svc> svcs;
   std::vector<IPAddr> node_port_addrs;
   bool any_node_port = false;
@@ -681,12 +717,24 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
         // a NodePort Service (ToNodePortAddressRegMark, no Service IP) is keyed by address 0
         const bool node_port = (f.m.reg_present & (1u << 4)) && (f.m.reg_m[4] & kToNodePort) && (f.m.reg_v[4] & kToNodePort);
         any_node_port |= node_port;
-        Svc s{f.m.nw_proto, f.m.tp_dst, {0, 0, 0, 0}, 0, false};
-        if (!node_port) words_of(f.m.nw_dst.addr.b, s.a);
+        Svc s{f.m.nw_proto, f.m.tp_dst, {0, 0, 0, 0}, 0, false, false};
+        if (!node_port && f.m.nw_dst.set) words_of(f.m.nw_dst.addr.b, s.a);
+        if (!f.acts.empty() && f.acts[0].kind == ACT_LEARN) {  // learn(...), EpSelected, goto EndpointDNAT
+          const Action& l = f.acts[0];
+          if ((f.m.reg_v[4] & kEpStateMask) != kEpToLearn || node_port == f.m.nw_dst.set || !f.m.has_tp_dst ||
+              f.m.tp_dst_m != 0xffff || !l.a || !l.lm || l.lm > kMaxInstallId || !(l.c & 2u) || f.acts.back().kind != ACT_GOTO ||
+              f.acts.back().a != TB_ENDPOINT_DNAT) {
+            *err = "unsupported ServiceLB learn flow: " + f.str();
+            return -GPC_EINVAL;
+          }
+          learn[SvcKey{s.proto, s.port, {s.a[0], s.a[1], s.a[2], s.a[3]}}] = Learn{l.a, uint32_t(l.lm)};
+          continue;
+        }
         bool grp = false;
         for (auto& a : f.acts) {
           if (a.kind == ACT_GROUP) s.gid = a.a, grp = true;
           if (a.kind == ACT_SET_REG && a.a == 7) s.reg7 = true;
+          if (a.kind == ACT_SET_REG && a.a == 4 && a.c == kEpStateMask) s.aff = a.b == kEpToLearn;
         }
         if (!grp || node_port == f.m.nw_dst.set || (f.m.nw_dst.set && f.m.nw_dst.plen >= 0) || !f.m.has_tp_dst ||
             f.m.tp_dst_m != 0xffff) {
@@ -696,9 +744,15 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
         svcs.push_back(s);
       }
     }
-  std::vector<uint32_t> svc_words, ep_words;
+  std::vector<uint32_t> svc_words, ep_words, aff_ids;
+  uint32_t n_aff = 0;
   std::vector<std::pair<uint64_t, uint32_t>> kv;
   for (auto& s : svcs) {
+    const auto lit = learn.find(SvcKey{s.proto, s.port, {s.a[0], s.a[1], s.a[2], s.a[3]}});
+    if (s.aff && lit == learn.end()) {
+      *err = "ServiceLB flow loads EpToLearnRegMark without a learn flow (group " + std::to_string(s.gid) + ")";
+      return -GPC_EINVAL;
+    }
     uint32_t first = uint32_t(ep_words.size() / kSvc6EpWords), n = 0;
     auto git = groups_.find(s.gid);
     if (git != groups_.end() && group_is_v4(git->second)) {
@@ -710,7 +764,7 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
         IPAddr ip;
         ip.fam = 6;
         uint32_t port = 0, flags = 0;
-        bool noep = false, to_dnat = false;
+        bool noep = false, to_dnat = false, to_lb = false;
         for (auto& a : b.acts) {
           if (a.kind == ACT_SET_XXREG3)
             for (int k = 0; k < 8; k++) {
@@ -720,10 +774,16 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
           if (a.kind == ACT_SET_REG && a.a == 4 && a.c == 0xffffu) port = a.b;
           if (a.kind == ACT_SET_REG && a.a == 4 && (a.b & kRemoteEndpoint)) flags |= GPC_LB_REMOTE;
           if (a.kind == ACT_SET_REG && a.a == 0 && (a.b & kSvcNoEp)) noep = true;
-          if (a.kind == ACT_RESUBMIT) to_dnat = a.a == TB_ENDPOINT_DNAT;
+          if (a.kind == ACT_RESUBMIT) to_dnat = a.a == TB_ENDPOINT_DNAT, to_lb = a.a == TB_SERVICE_LB;
         }
-        if (!to_dnat) {
+        // a session-affinity bucket resubmits to ServiceLB, where the Service's learn flow takes the
+        // packet on to EndpointDNAT (build_image)
+        if (!(to_dnat || (to_lb && s.aff)) || (to_lb && noep)) {
           *err = "unsupported group bucket (session affinity): " + git->second.str();
+          return -GPC_EINVAL;
+        }
+        if (s.aff && to_dnat && !noep) {
+          *err = "session-affinity Service whose group bypasses its learn flow: " + git->second.str();
           return -GPC_EINVAL;
         }
         if (noep) continue;
@@ -749,7 +809,10 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
       return -GPC_EINVAL;
     }
     kv.push_back({svc6_hash_key(s.proto, s.a, s.port), uint32_t(svc_words.size() / 4)});
-    svc_words.insert(svc_words.end(), {first, n | (lg << 24), s.gid, s.reg7 ? kSvcLoadReg7 : 0u});
+    svc_words.insert(svc_words.end(), {first, n | (lg << 24), s.gid,
+                                       (s.reg7 ? kSvcLoadReg7 : 0u) | (s.aff ? kSvcAffinity | (lit->second.timeout << 16) : 0u)});
+    aff_ids.push_back(s.aff ? lit->second.install : 0u);
+    n_aff += s.aff;
   }
   SvcHash h;
   if (!h.build(kv)) {
@@ -774,8 +837,19 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
   }
   hdr.np_off = hdr.ep_off + uint32_t(ep_words.size());
   hdr.n_np = uint32_t(node_port_addrs.size());
-  blob->assign(hdr.np_off + 4 * node_port_addrs.size(), 0u);
+  // session affinity: the install id of every Service (0: none) and the id of every NodePort
+  // address, after the rest -- an image without an affinity Service has neither
+  hdr.n_aff = n_aff;
+  hdr.aff_off = n_aff ? hdr.np_off + 4 * hdr.n_np : 0u;
+  blob->assign(hdr.np_off + 4 * node_port_addrs.size() + (n_aff ? aff_ids.size() + node_port_addrs.size() : 0), 0u);
   for (size_t i = 0; i < node_port_addrs.size(); i++) words_of(node_port_addrs[i].b, blob->data() + hdr.np_off + 4 * i);
+  if (n_aff) {
+    std::copy(aff_ids.begin(), aff_ids.end(), blob->begin() + hdr.aff_off);
+    for (size_t i = 0; i < node_port_addrs.size(); i++) {
+      const auto it = np_ids6_.find(node_port_addrs[i]);
+      (*blob)[hdr.aff_off + aff_ids.size() + i] = it == np_ids6_.end() ? 0u : it->second;
+    }
+  }
   std::memcpy(blob->data(), &hdr, sizeof hdr);
   for (auto& e : kv) {
     const uint32_t mb = svc_map_bit(e.first, hdr.map_log2);

@@ -36,6 +36,9 @@ class FeatureService {
   // Session affinity (gpc_config.session_affinity): the destination a learned flow of install id
   // `install` and NodePort address id `np_id` matches (NXM_OF_IP_DST); 0 when no longer realized.
   uint32_t affinity_dst(uint32_t install, uint32_t np_id) const;
+  // The same for an IPv6 learn flow (gpc_config.session_affinity6; NXM_NX_IPV6_DST): 16 bytes into
+  // out, false (and zeros) when no longer realized.
+  bool affinity_dst6(uint32_t install, uint32_t np_id, uint8_t* out) const;
   uint64_t generation() const { return generation_; }
 
   // Device Service image (core.hpp "Service image"), IPv4. Returns -GPC_EINVAL with *err for a
@@ -64,6 +67,7 @@ class FeatureService {
   // address ever set, 8 bits, never reused (the learned flows' NXM_OF_IP_DST of a NodePort Service).
   uint32_t next_install_ = 0;
   std::map<uint32_t, uint32_t> np_ids_;
+  std::map<IPAddr, uint32_t> np_ids6_;  // the same for the IPv6 NodePort addresses (session_affinity6)
 };
 
 }  // namespace gpc

@@ -44,6 +44,9 @@ LB_AFFINITY, LB_LEARNED = 0x10, 0x20  # session affinity: Endpoint from a learne
 # gpc_affinity_entry (gpc_debug_affinity_table)
 AFF_ENTRY_DTYPE = np.dtype([("install_id", "<u4"), ("src", "<u4"), ("dst", "<u4"), ("endpoint_ip", "<u4"),
                             ("endpoint_port", "<u4"), ("expires", "<u4")])
+# gpc_affinity_entry6 (gpc_debug_affinity_table6)
+AFF_ENTRY6_DTYPE = np.dtype([("install_id", "<u4"), ("endpoint_port", "<u4"), ("expires", "<u4"), ("reserved", "<u4"),
+                             ("src", "u1", (16,)), ("dst", "u1", (16,)), ("endpoint_ip", "u1", (16,))])
 VFLAG_PASS, VFLAG_TIE, VFLAG_PACKETIN = 1, 2, 4  # gpc_verdict.flags
 VTABLE_ENDPOINT_DNAT = 4
 
@@ -53,7 +56,7 @@ class gpc_config(C.Structure):
                 ("enable_deny_tracking", C.c_int32), ("cookie", C.c_uint64), ("device", C.c_int32),
                 ("compact_after", C.c_int32), ("ovs_meters", C.c_int32), ("external_node", C.c_int32),
                 ("group_packets", C.c_int32), ("group_key", C.c_int32), ("launch_pacing", C.c_int32),
-                ("session_affinity", C.c_int32)]
+                ("session_affinity", C.c_int32), ("session_affinity6", C.c_int32)]
 
 
 class gpc_addr(C.Structure):
@@ -144,7 +147,9 @@ EXPORTS = ["gpc_create", "gpc_destroy", "gpc_initialize", "gpc_install_rule", "g
            "gpc_set_launch_timing", "gpc_launch_times", "gpc_create_multi", "gpc_n_devices", "gpc_classify_on",
            "gpc_classify6_on", "gpc_classify_host_on", "gpc_counters_on", "gpc_debug_epoch6", "gpc_debug_fail_uploads",
            "gpc_classify6_lb", "gpc_classify6_lb_on", "gpc_classify6_host_lb", "gpc_debug_service_image6",
-           "gpc_set_affinity_clock", "gpc_affinity_stats", "gpc_debug_affinity_table", "gpc_debug_set_affinity_seq"]
+           "gpc_set_affinity_clock", "gpc_affinity_stats", "gpc_debug_affinity_table", "gpc_debug_set_affinity_seq",
+           "gpc_affinity_stats6", "gpc_debug_affinity_table6", "gpc_debug_set_affinity_seq6",
+           "gpc_debug_set_affinity6_digest_bits"]
 
 _lib = None
 
@@ -224,6 +229,10 @@ def load(path: str = LIB_PATH):
     lib.gpc_affinity_stats.argtypes = [vp, C.c_uint32, C.POINTER(gpc_affinity_counts)]
     lib.gpc_debug_affinity_table.argtypes = [vp, C.c_uint32, vp, sz, C.POINTER(sz)]
     lib.gpc_debug_set_affinity_seq.argtypes = [vp, C.c_uint32, C.c_uint32]
+    lib.gpc_affinity_stats6.argtypes = [vp, C.c_uint32, C.POINTER(gpc_affinity_counts)]
+    lib.gpc_debug_affinity_table6.argtypes = [vp, C.c_uint32, vp, sz, C.POINTER(sz)]
+    lib.gpc_debug_set_affinity_seq6.argtypes = [vp, C.c_uint32, C.c_uint32]
+    lib.gpc_debug_set_affinity6_digest_bits.argtypes = [vp, C.c_uint32, C.c_uint32]
     lib.gpc_strerror.argtypes = [i32]
     lib.gpc_strerror.restype = C.c_char_p
     _lib = lib
@@ -414,7 +423,7 @@ class Classifier:
 
     def __init__(self, ipv4=True, ipv6=False, enable_antrea_policy=True, enable_deny_tracking=False,
                  cookie=0x1020000000000, device=0, compact_after=0, ovs_meters=False, k8s_node=True, group_packets=0,
-                 group_key=0, devices=None, launch_pacing=0, session_affinity=0):
+                 group_key=0, devices=None, launch_pacing=0, session_affinity=0, session_affinity6=0):
         self.lib = load()
         cfg = gpc_config(ipv4_enabled=int(ipv4), ipv6_enabled=int(ipv6),
                          enable_antrea_policy=int(enable_antrea_policy),
@@ -422,7 +431,7 @@ class Classifier:
                          compact_after=int(compact_after), ovs_meters=int(ovs_meters),
                          external_node=int(not k8s_node), group_packets=int(group_packets),
                          group_key=int(group_key), launch_pacing=int(launch_pacing),
-                         session_affinity=int(session_affinity))
+                         session_affinity=int(session_affinity), session_affinity6=int(session_affinity6))
         h = C.c_void_p()
         if devices is None:
             _check(self.lib.gpc_create(C.byref(cfg), C.byref(h)), "gpc_create")
@@ -640,6 +649,33 @@ class Classifier:
         """Test hook: the launch sequence number of the slot's last affinity batch."""
         _check(self.lib.gpc_debug_set_affinity_seq(self.h, int(slot), int(seq)), "gpc_debug_set_affinity_seq")
 
+    # --- session affinity of IPv6 Services (gpc_config.session_affinity6): the slot's IPv6 table
+    def affinity_stats6(self, slot=0) -> dict:
+        st = gpc_affinity_counts()
+        _check(self.lib.gpc_affinity_stats6(self.h, int(slot), C.byref(st)), "gpc_affinity_stats6")
+        return {k: getattr(st, k) for k in ("slots", "live", "learned", "hits", "overflow", "sweeps")}
+
+    def affinity_table6(self, slot=0) -> np.ndarray:
+        """Host copy of the live learned entries of a slot's IPv6 table (AFF_ENTRY6_DTYPE)."""
+        n = C.c_size_t()
+        rc = self.lib.gpc_debug_affinity_table6(self.h, int(slot), None, 0, C.byref(n))
+        if rc not in (0, -GPC_ERANGE):
+            _check(rc, "gpc_debug_affinity_table6")
+        buf = np.zeros(n.value, dtype=AFF_ENTRY6_DTYPE)
+        if n.value:
+            _check(self.lib.gpc_debug_affinity_table6(self.h, int(slot), buf.ctypes.data, n.value, C.byref(n)),
+                   "gpc_debug_affinity_table6")
+        return buf
+
+    def debug_set_affinity_seq6(self, seq, slot=0):
+        """Test hook: the launch sequence number of the slot's last IPv6 affinity batch."""
+        _check(self.lib.gpc_debug_set_affinity_seq6(self.h, int(slot), int(seq)), "gpc_debug_set_affinity_seq6")
+
+    def debug_set_affinity6_digest_bits(self, bits, slot=0):
+        """Test hook: keep only `bits` low bits of the IPv6 table's claim digest (before its first use)."""
+        _check(self.lib.gpc_debug_set_affinity6_digest_bits(self.h, int(slot), int(bits)),
+               "gpc_debug_set_affinity6_digest_bits")
+
     def dump_groups(self) -> List[str]:
         need = C.c_size_t()
         self.lib.gpc_dump_groups(self.h, None, 0, C.byref(need))
@@ -698,6 +734,12 @@ class Classifier:
     def classify6_device(self, soa: gpc_pkt_soa, n: int, out_ptr: int, count=False, stream: int = 0, slot=0):
         _check(self.lib.gpc_classify6_on(self.h, int(slot), C.byref(soa), n, out_ptr, int(count), stream or None),
                "gpc_classify6")
+
+    def classify6_lb_device(self, soa: gpc_pkt_soa, n: int, out_ptr: int, lb_ptr: int = 0, count=False, stream: int = 0,
+                            slot=0):
+        """gpc_classify6_lb_on: device columns, the Service stage's results to lb_ptr (n gpc_lb_result6, 16-B aligned)."""
+        _check(self.lib.gpc_classify6_lb_on(self.h, int(slot), C.byref(soa), n, out_ptr, lb_ptr or None, int(count),
+                                            stream or None), "gpc_classify6_lb")
 
     def debug_image6(self):
         """(blob pointer, n_words, hdr pointer) of the committed IPv6 image (None when absent)."""

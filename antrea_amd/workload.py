@@ -567,6 +567,8 @@ def services_to_ipv6(wl: Workload, embed="96") -> Workload:
     if getattr(wl, "node_port_addresses", None):
         out.node_port_addresses = [e(a) for a in wl.node_port_addresses]
     out.svc_meta, out.svc_frac = copy.copy(wl.svc_meta), wl.svc_frac
+    if getattr(wl, "affinity_groups", None):  # session affinity (the configs carry affinity_timeout over as they are)
+        out.affinity_groups = set(wl.affinity_groups)
     return out
 
 

@@ -147,6 +147,12 @@ typedef struct gpc_config {
                                     SessionAffinity table, kept on the device): 0 = off (configs with
                                     affinity_timeout are rejected), n in [8, 26] = a table of 2^n entries
                                     (32 B each) per device slot; anything else fails gpc_create          */
+  int32_t session_affinity6;     /* the same for IPv6 Services, a table of its own (appended at the end of the
+                                    struct, as session_affinity was: the ABI version stays 6): 0 = off
+                                    (family-6 configs with affinity_timeout are rejected), n in [8, 26] = a
+                                    table of 2^n entries (64 B each: the key holds the 128-bit client
+                                    address) per device slot; anything else fails gpc_create. Independent of
+                                    session_affinity; each table is allocated by its first batch that needs it */
 } gpc_config;
 
 /* Order a grouped batch is classified in, inside every tile of 16384 packets (results never depend
@@ -426,8 +432,10 @@ int gpc_uninstall_endpoint_flows(gpc_ctx* ctx, uint8_t protocol, uint8_t family,
  * beside it. Its learned flows live in the device's affinity table: keyed by (this install, client
  * nw_src, packet nw_dst), value = the Endpoint, hard timeout T seconds of gpc_set_affinity_clock.
  * Every install of an affinity config gets a fresh install id (24 bits, never reused), so a
- * reinstall or uninstall orphans the entries learned so far (delete_learned). A family-6 config with
- * affinity_timeout, or any with session_affinity == 0: -GPC_EINVAL. A NodePort Service (is_nodeport; the caller passes the
+ * reinstall or uninstall orphans the entries learned so far (delete_learned). Family-6 configs take
+ * the same path (learn flow with eth_type=0x86dd, NXM_NX_IPV6_DST / _SRC and xxreg3; install ids from
+ * the same sequence) in a context created with gpc_config.session_affinity6. A config with
+ * affinity_timeout whose family's field is 0: -GPC_EINVAL. A NodePort Service (is_nodeport; the caller passes the
  * virtual NodePort DNAT IP 169.254.0.252 as its ip, as the proxier does) matches packets to the
  * NodePort addresses (gpc_set_node_port_addresses) by protocol and port (pipeline.go:2381-2387).
  * Both families take the same shapes: a family-6 config, Endpoint or Pod realizes the tcp6 / udp6 /
@@ -479,6 +487,27 @@ int gpc_debug_affinity_table(gpc_ctx* ctx, uint32_t slot, gpc_affinity_entry* bu
  * the bid words are reset when it is about to wrap), so a test can cross the wrap without 2^32
  * batches. -GPC_EINVAL before the slot's table exists (its first use restarts the sequence). */
 int gpc_debug_set_affinity_seq(gpc_ctx* ctx, uint32_t slot, uint32_t seq);
+/* The IPv6 table (gpc_config.session_affinity6): the same calls over the slot's IPv6 affinity table.
+ * slots = 2^session_affinity6; overflow also counts the +new packets whose key met another key's
+ * claim digest (below) and so was not learned. The clock is gpc_set_affinity_clock's. */
+int gpc_affinity_stats6(gpc_ctx* ctx, uint32_t slot, gpc_affinity_counts* out);
+typedef struct gpc_affinity_entry6 { /* one learned flow of an IPv6 Service; addresses in network byte order */
+  uint32_t install_id;
+  uint32_t endpoint_port;           /* reg4[0..15] | GPC_LB_REMOTE << 16                              */
+  uint32_t expires;
+  uint32_t reserved;
+  uint8_t src[16];                  /* client address (NXM_NX_IPV6_SRC)                                */
+  uint8_t dst[16];                  /* Service IP or NodePort address (NXM_NX_IPV6_DST; all 0: no longer known) */
+  uint8_t endpoint_ip[16];
+} gpc_affinity_entry6;
+int gpc_debug_affinity_table6(gpc_ctx* ctx, uint32_t slot, gpc_affinity_entry6* buf, size_t cap, size_t* n);
+int gpc_debug_set_affinity_seq6(gpc_ctx* ctx, uint32_t slot, uint32_t seq);
+/* Test hook: a slot of the IPv6 table is claimed by a 64-bit digest of (install id, NodePort address
+ * id, client address) and verified by the key itself; `bits` in [1, 64] keeps that many low bits of
+ * the digest for the slot's table (64 in production), so that a test meets digest collisions.
+ * -GPC_EINVAL once the slot's table exists (gpc_replay drops it), with the feature off, or for
+ * bits out of range. */
+int gpc_debug_set_affinity6_digest_bits(gpc_ctx* ctx, uint32_t slot, uint32_t bits);
 /* ovs-ofctl dump-groups style text of the realized groups, '\n' separated. */
 int gpc_dump_groups(gpc_ctx* ctx, char* buf, size_t cap, size_t* needed);
 
@@ -555,7 +584,12 @@ int gpc_trace(gpc_ctx* ctx, const gpc_pkt_soa* pkt, gpc_verdict* out, gpc_lb_res
  * XOR of each address's four 32-bit words), DNATed, and classified with ipv6_dst / tp_dst = the
  * Endpoint, ct_ipv6_dst = the original destination (unless ct_dst6 is given), reg7, reg1 and the
  * destination from the IPv6 Pod map; a Service without Endpoints is rejected as in gpc_classify_lb.
- * Without IPv6 Services the launches are those of a context that never had any. -GPC_EINVAL if the IPv6 prefixes of the rule set need more
+ * Without IPv6 Services the launches are those of a context that never had any. Session affinity
+ * (gpc_config.session_affinity6 and an IPv6 affinity Service committed): the semantics of
+ * gpc_classify_lb, per packet and in caller order, with GPC_LB_AFFINITY / GPC_LB_LEARNED in
+ * gpc_lb_result6.flags; aff6_learn and aff6_resolve (aff6_sweep once per clock value) run in the
+ * place of v6_lb, and without an IPv6 affinity Service the launches are those of a context without
+ * the field. The IPv6 table is the slot's own: gpc_replay drops it, commits leave it alone. -GPC_EINVAL if the IPv6 prefixes of the rule set need more
  * than 32 code bits (core.hpp). */
 int gpc_classify6(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out, int32_t count, void* stream);
 /* gpc_classify6 with the Service stage's selection in lb_out (device, n entries, 16-byte aligned,

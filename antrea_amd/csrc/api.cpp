@@ -1905,6 +1905,15 @@ int gpc_counters_on(gpc_ctx* ctx, uint32_t slot, uint64_t** dev, const uint32_t*
   return GPC_OK;
 }
 
+int gpc_debug_counter_layout(gpc_ctx* ctx, uint32_t slot, size_t* cap, uint32_t* copies) {
+  if (!ctx || slot >= ctx->dev.size()) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> g(ctx->ctl);
+  const DevState& D = ctx->dev[slot];
+  if (cap) *cap = D.d_counters ? D.counter_cap : 0;
+  if (copies) *copies = D.d_counters ? D.counter_copies : 0;
+  return GPC_OK;
+}
+
 int gpc_reset_counters(gpc_ctx* ctx) {
   if (!ctx) return -GPC_EINVAL;
   std::lock_guard<std::mutex> g(ctx->ctl);
@@ -2539,6 +2548,11 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
         for (uint32_t r = 0; r <= D.counter_copies; r++)  // (the published array too)
           (void)hipMemsetAsync(D.d_counters + kCounterWords * (size_t(r) * D.counter_cap + s), 0, kCounterBytes,
                                D.ustream);
+    // A released slot may already belong to a rule installed in this commit (SlotMap reuses LIFO),
+    // and no classify stream waits on the upload stream: the zeroing is complete before the commit
+    // returns, so a batch launched after it never has its first counts erased. Commits that
+    // release nothing (every address delta) do not wait.
+    if (!ctx->released_slots.empty() && D.d_counters) (void)hipStreamSynchronize(D.ustream);
   }
   ctx->released_slots.clear();
   if (std::getenv("GPC_COMPACT_DEBUG")) {

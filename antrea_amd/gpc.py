@@ -149,7 +149,7 @@ EXPORTS = ["gpc_create", "gpc_destroy", "gpc_initialize", "gpc_install_rule", "g
            "gpc_classify6_lb", "gpc_classify6_lb_on", "gpc_classify6_host_lb", "gpc_debug_service_image6",
            "gpc_set_affinity_clock", "gpc_affinity_stats", "gpc_debug_affinity_table", "gpc_debug_set_affinity_seq",
            "gpc_affinity_stats6", "gpc_debug_affinity_table6", "gpc_debug_set_affinity_seq6",
-           "gpc_debug_set_affinity6_digest_bits"]
+           "gpc_debug_set_affinity6_digest_bits", "gpc_debug_counter_layout"]
 
 _lib = None
 
@@ -189,6 +189,7 @@ def load(path: str = LIB_PATH):
     lib.gpc_classify_host.argtypes = [vp, C.POINTER(gpc_pkt_soa), sz, vp, i32]
     lib.gpc_counters.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(sz)]
     lib.gpc_reset_counters.argtypes = [vp]
+    lib.gpc_debug_counter_layout.argtypes = [vp, C.c_uint32, C.POINTER(sz), C.POINTER(C.c_uint32)]
     lib.gpc_dump_flows.argtypes = [vp, C.c_char_p, sz, C.POINTER(sz)]
     lib.gpc_get_image_stats.argtypes = [vp, C.POINTER(gpc_image_stats)]
     lib.gpc_debug_image.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
@@ -797,6 +798,14 @@ class Classifier:
 
     def reset_counters(self):
         _check(self.lib.gpc_reset_counters(self.h), "gpc_reset_counters")
+
+    def debug_counter_layout(self, slot=0):
+        """Test hook: (slots the device counter array holds, accumulator replicas) of a device slot as
+        of the last commit; (0, 0) before the first."""
+        cap, copies = C.c_size_t(), C.c_uint32()
+        _check(self.lib.gpc_debug_counter_layout(self.h, int(slot), C.byref(cap), C.byref(copies)),
+               "gpc_debug_counter_layout")
+        return cap.value, copies.value
 
     # --- introspection
     def dump_flows(self) -> List[str]:

@@ -624,6 +624,11 @@ int gpc_counters(gpc_ctx* ctx, uint64_t** dev_counters, const uint32_t** slot_co
  * gpc_reset_counters zeroes every slot. */
 int gpc_counters_on(gpc_ctx* ctx, uint32_t slot, uint64_t** dev_counters, const uint32_t** slot_conj, size_t* n_slots);
 int gpc_reset_counters(gpc_ctx* ctx);
+/* Test hook: the layout of the slot's device counter array as of the last commit: *cap = slots it
+ * holds, *copies = accumulator replicas the kernels stripe their adds over (the published array
+ * follows them). Both 0 before the first commit; a commit that adds rules past cap allocates a
+ * larger array and merges the old one into it. -GPC_EINVAL for a slot out of range. */
+int gpc_debug_counter_layout(gpc_ctx* ctx, uint32_t slot, size_t* cap, uint32_t* copies);
 
 /* ---------------------------------------------------------------------------- introspection */
 /* ovs-ofctl style dump of the realized flow table (utils.go FlowModToString), '\n' separated. */

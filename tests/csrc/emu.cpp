@@ -127,6 +127,42 @@ extern "C" int emu_trace(const uint32_t* blob, const void* hdr, const uint32_t* 
   return 0;
 }
 
+// The code of n IPv6 addresses (16 network-order bytes each) through the instantiation the device runs
+// (classify.hip v6_code_kernel: one address per call, the length descriptors read from a copy, as the
+// kernel reads its LDS copy) into one[n], and through the paired instantiation emu_classify6 runs --
+// address i with address i + 1 (cyclic) -- into pair[2 n].
+extern "C" int emu_v6_codes(const uint32_t* blob, const void* hdr, const uint32_t* pool, uint32_t jhdr, const uint8_t* addrs,
+                            size_t n, uint32_t* one, uint32_t* pair) {
+  const ImageHdr* h = static_cast<const ImageHdr*>(hdr);
+  const V6Lpm* L = reinterpret_cast<const V6Lpm*>(blob + h->v6_lpm);
+  const std::vector<V6Len> desc(L->d, L->d + L->n_lens);
+  const uint32_t* ovf = nullptr;
+  uint32_t ovf_log2 = 0;
+  if (pool) {
+    const JournalHdr* jh = reinterpret_cast<const JournalHdr*>(pool + jhdr);
+    if (jh->v6_ovf_off) {
+      ovf = pool + jh->v6_ovf_off;
+      ovf_log2 = jh->v6_ovf_log2;
+    }
+  }
+  unsigned long long saved[16];
+  std::copy(::gpc_emu_stats, ::gpc_emu_stats + 16, saved);
+  for (size_t i = 0; i < n; i++) {
+    uint32_t a[2][4];
+    v6_words(addrs + 16 * i, a[0]);
+    v6_words(addrs + 16 * ((i + 1) % n), a[1]);
+    if (ovf) {
+      v6_codes<1, true>(blob, h->v6_lpm, a, one + i, ovf, ovf_log2, desc.data());
+      v6_codes<2, true>(blob, h->v6_lpm, a, pair + 2 * i, ovf, ovf_log2);
+    } else {
+      v6_codes<1>(blob, h->v6_lpm, a, one + i, nullptr, 0, desc.data());
+      v6_codes<2>(blob, h->v6_lpm, a, pair + 2 * i);
+    }
+  }
+  std::copy(saved, saved + 16, ::gpc_emu_stats);
+  return 0;
+}
+
 // IPv6 batch over the IPv6 image (gpc_debug_image6): addresses mapped to codes as the kernel does.
 extern "C" int emu_classify6(const uint32_t* blob, const void* hdr, const uint32_t* pool, uint32_t jhdr,
                              const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, unsigned long long* counters) {

@@ -37,7 +37,21 @@ def load():
                                C.POINTER(gpc.gpc_trace_step), C.POINTER(C.c_uint32)]
     _lib.emu_classify6.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(gpc.gpc_pkt_soa),
                                    C.c_size_t, C.c_void_p, C.c_void_p]
+    _lib.emu_v6_codes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     return _lib
+
+
+def v6_codes(clf: "gpc.Classifier", addrs):
+    """LPM codes of (n, 16) uint8 addresses in clf's committed IPv6 epoch: (one (n,), pair (n, 2)) --
+    the device's instantiation (one address per search, the length descriptors from a copy) and the
+    emulation's paired one over address i and address i + 1 (cyclic)."""
+    blob, nw, hdr = clf.debug_image6()
+    assert blob, "no IPv6 image"
+    pool, _, jhdr = clf.debug_epoch6()
+    a = np.ascontiguousarray(addrs, dtype=np.uint8).reshape(-1, 16)
+    one, pair = np.zeros(len(a), np.uint32), np.zeros((len(a), 2), np.uint32)
+    load().emu_v6_codes(blob, hdr, pool, jhdr, a.ctypes.data, len(a), one.ctypes.data, pair.ctypes.data)
+    return one, pair
 
 
 class _Counters:

@@ -7,7 +7,10 @@ CPU tier: the product's IPv6 image evaluated by the host emulation of the kernel
     metamorphic parity up to full C3 (100k rules), where the IPv4 side is itself pinned by the C
     oracle (tests/test_oracle_c.py);
   * the IPv6 flow dump equals the oracle compiler's.
-The GPU tier (tests/test_gpu_parity.py) checks gpc_classify6 against the same emulation."""
+The GPU tier checks gpc_classify6 against the same emulation: tests/test_gpu_parity.py (embedded
+workloads), test_gpu_group.py (grouped), test_gpu_service6.py / test_gpu_affinity6.py (Services) and
+test_gpu_v6_chain.py (native prefixes, batch sizes, column sets, scratch reuse, LPM layouts); native
+prefixes on the CPU tier are in tests/test_v6_native.py."""
 import copy
 import ipaddress
 

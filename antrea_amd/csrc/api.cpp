@@ -1624,10 +1624,16 @@ int gpc_classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n
 
 int gpc_trace(gpc_ctx* ctx, const gpc_pkt_soa* pk, gpc_verdict* out, gpc_lb_result* lb_out, gpc_trace_step* steps,
               size_t cap, size_t* n_steps) {
+  return gpc_trace_on(ctx, 0, pk, out, lb_out, steps, cap, n_steps);
+}
+
+int gpc_trace_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict* out, gpc_lb_result* lb_out,
+                 gpc_trace_step* steps, size_t cap, size_t* n_steps) {
   static_assert(sizeof(gpc_trace_step) == sizeof(TraceStep), "gpc_trace_step mirrors core.hpp TraceStep");
   if (!ctx || !pk || !out || !pk->src || !pk->dst || !pk->sport || !pk->dport || !pk->proto || !pk->out_port)
     return -GPC_EINVAL;
-  if (hip_ok(hipSetDevice(ctx->dev[0].device))) return -GPC_EDEV;
+  if (slot >= ctx->dev.size()) return -GPC_EINVAL;
+  if (hip_ok(hipSetDevice(ctx->dev[slot].device))) return -GPC_EDEV;
   // one packet: every present column's element 0 goes into one small device buffer
   struct Col {
     const void* h;
@@ -1659,13 +1665,13 @@ int gpc_trace(gpc_ctx* ctx, const gpc_pkt_soa* pk, gpc_verdict* out, gpc_lb_resu
   uint32_t* dn = reinterpret_cast<uint32_t*>(buf + 64 + kMaxTraceSteps * sizeof(TraceStep));
   if (!rc) {
     std::lock_guard<std::mutex> g(ctx->data);
-    const DevEpoch& cur = ctx->dev[0].cur;
+    const DevEpoch& cur = ctx->dev[slot].cur;
     if (!cur.base) {
       rc = -GPC_EINVAL;  // nothing committed yet
     } else {
       EpochArgs ep{cur.base->d_hdr, cur.base->d_blob, cur.jhdr ? cur.pool->d_blob : nullptr, cur.jhdr,
                    cur.svc ? cur.svc->d_blob : nullptr, 0u, {0, 0}, 0u, 0u};
-      DevState& D = ctx->dev[0];
+      DevState& D = ctx->dev[slot];
       uint8_t* ascr = nullptr;
       bool noep = false;
       // Session affinity with a table in use: the Service stage runs read-only over the table
@@ -1705,6 +1711,104 @@ int gpc_trace(gpc_ctx* ctx, const gpc_pkt_soa* pk, gpc_verdict* out, gpc_lb_resu
   if (n_steps) *n_steps = n;
   if (steps) std::memcpy(steps, h.data() + 64, std::min<size_t>(n, cap) * sizeof(TraceStep));
   return n > cap && steps ? -GPC_ERANGE : GPC_OK;
+}
+
+// Lock order: ctx->ctl, then ctx->data -- the order gpc_commit takes them in. `ctl` is held for the
+// whole call: the codes are translated through the prefix tree of the IPv6 host image
+// (last6.codes6), which a delta commit extends in place (V6Codes::add_leaf) and a full one replaces,
+// both under `ctl`; holding it from before the launch keeps the tree the one of the traced epoch.
+// `data` is held for the launch alone (the epoch stays alive while it is current).
+int gpc_trace6(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict* out, gpc_lb_result6* lb_out,
+               gpc_trace6_addr* addrs, gpc_trace_step* steps, size_t cap, size_t* n_steps) {
+  static_assert(sizeof(gpc_trace6_addr) == 32, "gpc.py gpc_trace6_addr");
+  if (!ctx || !pk || !out || slot >= ctx->dev.size()) return -GPC_EINVAL;
+  if (!pk->src6 || !pk->dst6 || !pk->sport || !pk->dport || !pk->proto || !pk->out_port) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> g(ctx->ctl);
+  {
+    std::lock_guard<std::mutex> d(ctx->data);
+    if (!ctx->dev[slot].cur.v6) return -GPC_EINVAL;  // IPv6 disabled or nothing committed yet
+  }
+  if (hip_ok(hipSetDevice(ctx->dev[slot].device))) return -GPC_EDEV;
+  // one packet: every present column's element 0 goes into one small device buffer, every column in
+  // a 16-B slot of its own (one 128-bit load per address, whatever the host pointers' alignment)
+  struct Col {
+    const void* h;
+    size_t elem;
+    const void** d;
+  };
+  gpc_pkt_soa d{};
+  Col cols[] = {{pk->src6, 16, (const void**)&d.src6},        {pk->dst6, 16, (const void**)&d.dst6},
+                {pk->ct_src6, 16, (const void**)&d.ct_src6},  {pk->ct_dst6, 16, (const void**)&d.ct_dst6},
+                {pk->sport, 2, (const void**)&d.sport},       {pk->dport, 2, (const void**)&d.dport},
+                {pk->proto, 1, (const void**)&d.proto},       {pk->out_port, 4, (const void**)&d.out_port},
+                {pk->in_port, 4, (const void**)&d.in_port},   {pk->svc_group, 4, (const void**)&d.svc_group},
+                {pk->tun_id, 4, (const void**)&d.tun_id},     {pk->ct_state, 1, (const void**)&d.ct_state},
+                {pk->dest, 1, (const void**)&d.dest},         {pk->len, 2, (const void**)&d.len},
+                {pk->ct_mark, 1, (const void**)&d.ct_mark}};
+  // outputs: verdicts [0, 16), LB result [16, 48), codes and their bits [48, 80), step count [80, 84), steps [96, ..)
+  constexpr size_t kSlot = 16, kLb = 16, kCodes = 48, kCount = 80, kSteps = 96, kOut = 512;
+  static_assert(kSteps + kMaxTraceSteps * sizeof(TraceStep) <= kOut, "the steps fit in front of the column slots");
+  const size_t ncol = sizeof cols / sizeof cols[0];
+  std::vector<uint8_t> h(kOut + ncol * kSlot, 0);
+  for (size_t c = 0; c < ncol; c++)
+    if (cols[c].h) std::memcpy(h.data() + kOut + c * kSlot, cols[c].h, cols[c].elem);
+  uint8_t* buf = nullptr;
+  if (hip_ok(hipMalloc(&buf, h.size()))) return -GPC_EDEV;
+  for (size_t c = 0; c < ncol; c++)
+    if (cols[c].h) *cols[c].d = buf + kOut + c * kSlot;
+  int rc = hip_ok(hipMemcpy(buf, h.data(), h.size(), hipMemcpyHostToDevice));
+  if (!rc) {
+    std::lock_guard<std::mutex> dl(ctx->data);
+    DevState& D = ctx->dev[slot];
+    const DevEpoch& cur = D.cur;
+    EpochArgs ep{cur.v6->d_hdr, cur.v6->d_blob, cur.v6_jhdr ? cur.v6_pool->d_blob : nullptr, cur.v6_jhdr,
+                 nullptr, cur.v6_lpm, {0, 0}, 0u, 0u};
+    Trace6Args t{};
+    t.svc6 = cur.svc6 ? cur.svc6->d_blob : nullptr;
+    t.out = reinterpret_cast<uint4*>(buf);
+    t.lb_out = reinterpret_cast<uint4*>(buf + kLb);
+    t.codes = reinterpret_cast<uint32_t*>(buf + kCodes);
+    t.n_steps = reinterpret_cast<uint32_t*>(buf + kCount);
+    t.steps = reinterpret_cast<TraceStep*>(buf + kSteps);
+    // Session affinity with a table in use: the kernel reads it (lb_stage6_aff<true>) once the slot's
+    // pending affinity batch is through; nothing here advances the sequence, the sweep clock or a counter
+    if (cur.svc6 && cur.svc6->affinity && ctx->cfg.session_affinity6 && D.a6.tab) {
+      t.tab = aff6_table(ctx, D);
+      t.now = aff_now(ctx);
+      if (D.a6.done && hip_ok(hipStreamWaitEvent(nullptr, D.a6.done, 0))) rc = -GPC_EDEV;
+    }
+    if (!rc) rc = launch_trace6(ep, d, t, nullptr);
+    if (!rc) rc = hip_ok(hipDeviceSynchronize());
+  }
+  if (!rc) rc = hip_ok(hipMemcpy(h.data(), buf, kOut, hipMemcpyDeviceToHost));
+  (void)hipFree(buf);
+  if (rc) return rc;
+  std::memcpy(out, h.data(), 2 * sizeof(gpc_verdict));
+  if (lb_out) std::memcpy(lb_out, h.data() + kLb, sizeof(gpc_lb_result6));
+  uint32_t n = 0, codes[8];
+  std::memcpy(&n, h.data() + kCount, 4);
+  std::memcpy(codes, h.data() + kCodes, sizeof codes);
+  if (n_steps) *n_steps = n;
+  if (steps) std::memcpy(steps, h.data() + kSteps, std::min<size_t>(n, cap) * sizeof(TraceStep));
+  if (addrs) {
+    for (int k = 0; k < 4; k++) {
+      gpc_trace6_addr& a = addrs[k];
+      a = gpc_trace6_addr{};
+      if (!(codes[4 + k] & GPC_T6_PRESENT)) continue;
+      a.code = codes[k];
+      a.flags = codes[4 + k];
+      if (v6_prefix_of_code(ctx->last6, codes[k], a.prefix, &a.prefix_len)) rc = -GPC_EINVAL;
+    }
+  }
+  if (rc) return rc;
+  return n > cap && steps ? -GPC_ERANGE : GPC_OK;
+}
+
+int gpc_debug_v6_prefix_of_code(gpc_ctx* ctx, uint32_t code, uint8_t prefix[16], uint32_t* prefix_len) {
+  if (!ctx || !prefix || !prefix_len) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> g(ctx->ctl);
+  if (ctx->last6.blob.empty()) return -GPC_EINVAL;  // no IPv6 image
+  return v6_prefix_of_code(ctx->last6, code, prefix, prefix_len);
 }
 
 int gpc_classify_host(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, int32_t count) {

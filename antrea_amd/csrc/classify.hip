@@ -815,6 +815,95 @@ int launch_trace(const EpochArgs& ep, const gpc_pkt_soa& pk, uint4* out, uint4* 
   return hipGetLastError() == hipSuccess ? 0 : -GPC_EDEV;
 }
 
+// gpc_trace6: one IPv6 packet through the stages of an IPv6 batch, in one launch, so the trace sees
+// one epoch: the Service stage on the 128-bit addresses (v6_lb_kernel's lb_stage6, or with an affinity
+// table aff6_resolve_kernel's lb_stage6_aff, read-only: no bid, no entry, no counter), the LPM coding
+// of the address columns (v6_code_kernel's v6_codes<1> / <1, true>, the length descriptors read from
+// the image) and the traced walk over the codes. One lane; debug path, not the data path.
+// codes[0..3]: the codes of src6, the post-DNAT dst6, ct_src6, ct_dst6 (or the pre-NAT destination
+// behind a Service image); codes[4..7]: their GPC_T6_* bits. OVERFLOW: the journal's overflow table
+// decided the code -- the search over the base tables alone ends at another one (a prefix interned
+// since the base has a code of its own, and every other address keeps its base code).
+__global__ void trace6_kernel(EpochArgs ep, gpc_pkt_soa pk, Trace6Args t) {
+  __shared__ uint32_t pkt_lds[kPktWords];
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  uint32_t a[4][4];
+  bool present[4] = {true, true, pk.ct_src6 != nullptr, pk.ct_dst6 != nullptr || t.svc6 != nullptr};
+  aff6_addr(pk.src6, 0, a[0]);
+  aff6_addr(pk.dst6, 0, a[1]);
+  if (pk.ct_src6) aff6_addr(pk.ct_src6, 0, a[2]);
+  if (pk.ct_dst6) aff6_addr(pk.ct_dst6, 0, a[3]);
+  else
+    for (int w = 0; w < 4; w++) a[3][w] = a[1][w];  // ct_ipv6_dst: the destination before the DNAT
+  uint32_t dport = pk.dport[0];
+  const uint32_t sport = pk.sport[0], proto = pk.proto[0];
+  uint32_t out_port = pk.out_port[0], svc_group = pk.svc_group ? pk.svc_group[0] : 0u, dest = pk.dest ? pk.dest[0] : 0u;
+  const uint32_t ct_mark = pk.ct_mark ? pk.ct_mark[0] : 0u;
+  uint32_t lb[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, f = 0;
+  *t.n_steps = 0;
+  for (int k = 0; k < 8; k++) t.codes[k] = 0;
+  if (t.svc6) {
+    if (t.tab.w) {
+      const Aff6Cols cols{pk.src6, pk.dst6, pk.sport, pk.dport, pk.proto, pk.ct_state, 1u};
+      bool collided;
+      f = lb_stage6_aff<true>(t.svc6, t.tab, t.now, 0u, 0u, cols, a[1], dport, proto, svc_group, out_port, dest, lb, &collided);
+    } else {
+      f = lb_stage6(t.svc6, [&]() { return Svc6Src{fold6(a[0]), sport}; }, a[1], dport, proto, svc_group, out_port, dest, lb);
+    }
+    dest &= ~kDestNoEndpoint;
+  }
+  t.lb_out[0] = make_uint4(__builtin_bswap32(lb[0]), __builtin_bswap32(lb[1]), __builtin_bswap32(lb[2]), __builtin_bswap32(lb[3]));
+  t.lb_out[1] = make_uint4(lb[4], lb[5], lb[6], 0u);
+  if (f & GPC_LB_NO_ENDPOINT) {  // rejected in EndpointDNAT before any rule table
+    t.out[0] = make_uint4(0u, pack_verdict(GPC_ACT_REJECT, GPC_VTABLE_ENDPOINT_DNAT, 0, 0), 0u, 0u);
+    return;
+  }
+  const uint32_t* ovf = nullptr;
+  uint32_t ovf_log2 = 0;
+  if (ep.pool) {
+    const JournalHdr* jh = reinterpret_cast<const JournalHdr*>(ep.pool + ep.jhdr);
+    if (jh->v6_ovf_off) {
+      ovf = ep.pool + jh->v6_ovf_off;
+      ovf_log2 = jh->v6_ovf_log2;
+    }
+  }
+  uint32_t code[4] = {0u, 0u, 0u, 0u};
+#pragma nounroll
+  for (int k = 0; k < 4; k++) {
+    if (!present[k]) continue;
+    const uint32_t aa[1][4] = {{a[k][0], a[k][1], a[k][2], a[k][3]}};
+    uint32_t bits = GPC_T6_PRESENT | (k == 1 && (f & GPC_LB_DNAT) ? uint32_t(GPC_T6_DNAT) : 0u);
+    if (ovf) {
+      uint32_t base;
+      v6_codes<1, true>(ep.blob, ep.v6_lpm, aa, &code[k], ovf, ovf_log2);
+      v6_codes<1>(ep.blob, ep.v6_lpm, aa, &base);
+      if (base != code[k]) bits |= GPC_T6_OVERFLOW;
+    } else {
+      v6_codes<1>(ep.blob, ep.v6_lpm, aa, &code[k]);
+    }
+    t.codes[k] = code[k];
+    t.codes[4 + k] = bits;
+  }
+  View im{{ep.blob, const_hdr(ep.hdr), nullptr, ep.pool}, {ep.pool, nullptr, nullptr, ep.pool}, 1u, ep.jhdr, 0u};
+  if (ep.pool) {
+    const JournalHdr* jh = reinterpret_cast<const JournalHdr*>(ep.pool + ep.jhdr);
+    if (jh->bdead_off) im.base.dead = ep.pool + jh->bdead_off;
+    im.n_img = 2u;
+    im.ext = jh->ext_off;
+  }
+  Pkt p(pkt_lds, 1);
+  make_pkt(p, code[0], code[1], sport, dport, proto, out_port, pk.in_port ? pk.in_port[0] : 0u, svc_group,
+           pk.tun_id ? pk.tun_id[0] : 0u, present[2] ? code[2] : code[0], present[3] ? code[3] : code[1],
+           pk.ct_state ? pk.ct_state[0] : uint32_t(GPC_CT_NEW | GPC_CT_TRK), view_bloom_axes(im));
+  const PacketOut o = classify_packet<kModeJournal, 0, true>(im, p, dest, ct_mark, t.steps, t.n_steps);
+  t.out[0] = make_uint4(o.e.conj, o.e.packed, o.g.conj, o.g.packed);
+}
+
+int launch_trace6(const EpochArgs& ep, const gpc_pkt_soa& pk, const Trace6Args& t, hipStream_t stream) {
+  hipLaunchKernelGGL(trace6_kernel, dim3(1), dim3(64), 0, stream, ep, pk, t);
+  return hipGetLastError() == hipSuccess ? 0 : -GPC_EDEV;
+}
+
 // One thread per counter slot: the accumulator copies {packets, bytes, non-session packets} are
 // drained (atomic exchange: a classification running concurrently on another stream loses no
 // update, it lands in the next fold) and added to the published copy as {packets, bytes, sessions}.

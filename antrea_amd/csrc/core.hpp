@@ -2711,6 +2711,8 @@ GPC_HD void aff6_learn(const uint32_t* sv, const Aff6Table& t, uint32_t now, uin
 // lb_stage6 with the affinity branch (the resolve pass) of packet i: dst / dport are the packet's
 // own (rewritten by the DNAT), the winner's columns are read from pk. Returns the GPC_LB_* flags;
 // *collided: a +new packet whose key met another key's digest (counted by the caller).
+// kReadOnly (gpc_trace6): the bid word is ignored and nothing is written, as lb_stage_aff's read_only.
+template <bool kReadOnly = false>
 GPC_HD uint32_t lb_stage6_aff(const uint32_t* sv, const Aff6Table& t, uint32_t now, uint32_t seq, uint32_t i, const Aff6Cols& pk,
                               uint32_t* dst, uint32_t& dport, uint32_t proto, uint32_t& svc_group, uint32_t& out_port,
                               uint32_t& dest, uint32_t* o, bool* collided) {
@@ -2743,7 +2745,7 @@ GPC_HD uint32_t lb_stage6_aff(const uint32_t* sv, const Aff6Table& t, uint32_t n
     if (slot != kAffNone) {
       const uint32_t ct_state = pk.ct_state ? pk.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK);
       const uint64_t bid = *aff6_bid_word(t, slot);
-      if (uint32_t(bid >> 32) == ~seq && uint32_t(bid) < pk.n) {  // a bid of this launch: winner = its low half
+      if (!kReadOnly && uint32_t(bid >> 32) == ~seq && uint32_t(bid) < pk.n) {  // a bid of this launch: winner = its low half
         const uint32_t w = uint32_t(bid);
         // the winner's key is this packet's when client, destination, port and protocol agree
         uint32_t ws[4], wd[4];
@@ -2771,7 +2773,7 @@ GPC_HD uint32_t lb_stage6_aff(const uint32_t* sv, const Aff6Table& t, uint32_t n
   const uint32_t fdst = fold6(dst);  // the pre-NAT destination
   if (index == kAffNone) index = (lb_hash(fold6(src), fdst, pick_sport, dport, proto) & ((1u << lg) - 1u)) % n;
   const uint32_t* e = sv + h->ep_off + kSvc6EpWords * (size_t(s[0]) + index);
-  if (flags & GPC_LB_LEARNED) {  // the winner: no other lane reads or writes these words in this pass
+  if (!kReadOnly && (flags & GPC_LB_LEARNED)) {  // the winner: no other lane reads or writes these words in this pass
     uint32_t* b = aff6_body(t, slot);
     b[0] = src[0], b[1] = src[1], b[2] = src[2], b[3] = src[3];
     b[4] = e[0], b[5] = e[1], b[6] = e[2], b[7] = e[3];

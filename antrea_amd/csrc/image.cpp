@@ -353,6 +353,28 @@ class V6Codes {
     auto it = index_.find({v & v6_prefix_mask(len), len});
     return it == index_.end() ? -1 : it->second;
   }
+  // The node whose addresses get `code` from the LPM (gpc_trace6): the deepest node whose code range
+  // [code, code + 2^(32 - clen)) holds it -- the ranges of a node's children are disjoint and lie in
+  // the node's, so the descent takes at every node the one child that holds the code -- provided the
+  // code is that node's own (the node's code padded with zeros: its "none of the children" leaf, or
+  // the exact code of a childless node). -1: no node owns the code (free code space, or a range
+  // whose children tile it). The root (0) owns code 0: an address under no prefix.
+  int owner(uint32_t code) const {
+    int n = 0;
+    for (bool down = true; down;) {
+      down = false;
+      for (int k : nodes[size_t(n)].kids) {
+        const Node& K = nodes[size_t(k)];
+        const uint32_t mk = prefix_mask(K.clen);
+        if ((code & mk) == (K.code & mk)) {
+          n = k;
+          down = true;
+          break;
+        }
+      }
+    }
+    return nodes[size_t(n)].code == code ? n : -1;
+  }
 
  private:
   std::map<std::pair<u128, int>, int> index_;
@@ -2225,6 +2247,18 @@ int build_image6(const FeatureNP& np, SlotMap& slots, HostImage* out, bool alloc
   out->bytes_hash += 4ull * tab_words;
   out->v6_code_bits = uint32_t(codes.max_clen);
   out->v6_prefixes = uint32_t(codes.nodes.size() - 1);
+  return GPC_OK;
+}
+
+int v6_prefix_of_code(const HostImage& img, uint32_t code, uint8_t prefix[16], uint32_t* prefix_len) {
+  for (int i = 0; i < 16; i++) prefix[i] = 0;
+  *prefix_len = 0;
+  if (!img.codes6) return -GPC_EINVAL;
+  const int n = img.codes6->owner(code);
+  if (n < 0) return -GPC_EINVAL;
+  const V6Codes::Node& N = img.codes6->nodes[size_t(n)];
+  for (int i = 0; i < 16; i++) prefix[i] = uint8_t(N.v >> (8 * (15 - i)));
+  *prefix_len = uint32_t(N.len);
   return GPC_OK;
 }
 

@@ -93,6 +93,11 @@ class Journal;
 // overflow table (probed next to the base LPM hash by delta-epoch kernels). Nothing published is
 // rewritten. -GPC_EINVAL when a prefix cannot be interned (rebuild the IPv6 image instead).
 int extend_image6(const FeatureNP& np, const std::set<uint32_t>& conj, uint8_t hard_tables, HostImage* img, Journal* j6);
+// gpc_trace6's translation of an LPM code: the prefix (16 network-order bytes, host bits zero) of the
+// node of img's prefix tree that owns `code` (V6Codes::owner); *prefix_len = 0 for the code of an
+// address under no prefix. -GPC_EINVAL: no tree, or no node owns the code (outputs zeroed). The
+// caller holds what keeps delta commits from extending the tree meanwhile (api.cpp: ctx->ctl).
+int v6_prefix_of_code(const HostImage& img, uint32_t code, uint8_t prefix[16], uint32_t* prefix_len);
 // Append-only delta store over one base image (core.hpp "journal"). apply() appends the current
 // versions of the changed rules (records, driver-bucket entries, copied-on-write head pages) and a
 // new epoch header with the cumulative tombstones; nothing published earlier is rewritten, so the

@@ -88,6 +88,20 @@ int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc
                      unsigned long long* counters, int count, const GroupArgs* group, uint32_t* codes, hipStream_t stream,
                      LaunchMarks* marks = nullptr, const uint32_t* svc6 = nullptr, uint8_t* lb_scratch = nullptr,
                      uint4* lb_out6 = nullptr, const Aff6Launch* al = nullptr);
+// gpc_trace6: packet 0 of the device columns `pk` (src6 / dst6 [/ ct_src6 / ct_dst6], 16-B aligned)
+// through the IPv6 epoch `ep` in one launch (classify.hip trace6_kernel): Service stage, LPM coding,
+// traced walk.
+struct Trace6Args {
+  const uint32_t* svc6;  // the IPv6 Service image bound to the epoch (null: none)
+  Aff6Table tab;         // tab.w != null: the slot's IPv6 affinity table is read (never written)
+  uint32_t now;          // affinity clock
+  uint4* out;            // the verdict pair
+  uint4* lb_out;         // gpc_lb_result6 (two uint4; all zero: no Service hit)
+  uint32_t* codes;       // [0..3] codes of src, dst, ct_src, ct_dst; [4..7] their GPC_T6_* bits
+  TraceStep* steps;      // kMaxTraceSteps
+  uint32_t* n_steps;
+};
+int launch_trace6(const EpochArgs& ep, const gpc_pkt_soa& pk, const Trace6Args& t, hipStream_t stream);
 // One pass over the IPv6 affinity table's slots (core.hpp aff6_sweep_slot modes).
 int launch_aff6_sweep(const Aff6Table& t, uint32_t now, uint32_t mode, hipStream_t stream, LaunchMarks* marks = nullptr);
 // IPv4 batch against a Service image with session-affinity Services (ep.svc) and the slot's affinity

@@ -92,6 +92,14 @@ class gpc_trace_step(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("table", "verdict", "flags", "conj_id", "priority", "candidates")]
 
 
+class gpc_trace6_addr(C.Structure):
+    _fields_ = [("prefix", C.c_uint8 * 16), ("prefix_len", C.c_uint32), ("code", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+T6_PRESENT, T6_OVERFLOW, T6_DNAT = 1, 2, 4  # gpc_trace6_addr.flags
+
+
 class gpc_policy_info(C.Structure):
     _fields_ = [("found", C.c_int32), ("policy_type", C.c_uint8), ("of_priority", C.c_uint16),
                 ("policy_namespace", C.c_char * 64), ("policy_name", C.c_char * 128), ("policy_uid", C.c_char * 64),
@@ -149,7 +157,8 @@ EXPORTS = ["gpc_create", "gpc_destroy", "gpc_initialize", "gpc_install_rule", "g
            "gpc_classify6_lb", "gpc_classify6_lb_on", "gpc_classify6_host_lb", "gpc_debug_service_image6",
            "gpc_set_affinity_clock", "gpc_affinity_stats", "gpc_debug_affinity_table", "gpc_debug_set_affinity_seq",
            "gpc_affinity_stats6", "gpc_debug_affinity_table6", "gpc_debug_set_affinity_seq6",
-           "gpc_debug_set_affinity6_digest_bits", "gpc_debug_counter_layout"]
+           "gpc_debug_set_affinity6_digest_bits", "gpc_debug_counter_layout", "gpc_trace_on", "gpc_trace6",
+           "gpc_debug_v6_prefix_of_code"]
 
 _lib = None
 
@@ -224,6 +233,10 @@ def load(path: str = LIB_PATH):
                                                  C.POINTER(sz)]
     lib.gpc_stream_epoch.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     lib.gpc_trace.argtypes = [vp, C.POINTER(gpc_pkt_soa), vp, vp, C.POINTER(gpc_trace_step), sz, C.POINTER(sz)]
+    lib.gpc_trace_on.argtypes = [vp, C.c_uint32, C.POINTER(gpc_pkt_soa), vp, vp, C.POINTER(gpc_trace_step), sz, C.POINTER(sz)]
+    lib.gpc_trace6.argtypes = [vp, C.c_uint32, C.POINTER(gpc_pkt_soa), vp, vp, C.POINTER(gpc_trace6_addr),
+                               C.POINTER(gpc_trace_step), sz, C.POINTER(sz)]
+    lib.gpc_debug_v6_prefix_of_code.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
     lib.gpc_set_launch_timing.argtypes = [vp, C.c_uint32]
     lib.gpc_launch_times.argtypes = [vp, C.POINTER(gpc_launch_time), sz, C.POINTER(sz)]
     lib.gpc_set_affinity_clock.argtypes = [vp, C.c_uint32]
@@ -756,18 +769,48 @@ class Classifier:
         _check(self.lib.gpc_classify_on(self.h, int(slot), C.byref(soa), n, out_ptr, lb_ptr or None, int(count),
                                         stream or None), "gpc_classify")
 
-    def trace(self, pkt: Dict[str, int]):
-        """gpc_trace of one packet (dict of column values): (verdicts (2,), [step dicts], lb result)."""
+    _STEP_FIELDS = ("table", "verdict", "flags", "conj_id", "priority", "candidates")
+
+    def trace(self, pkt: Dict[str, int], slot=0):
+        """gpc_trace_on of one packet (dict of column values) on device slot `slot`: (verdicts (2,),
+        [step dicts], lb result)."""
         cols = {k: np.array([v], dtype=PKT_COLUMNS[k]) for k, v in pkt.items()}
         soa, keep, n = pkt_soa_host(cols)
         out = np.zeros(2, dtype=VERDICT_DTYPE)
         lb = np.zeros(1, dtype=LB_DTYPE)
         steps = (gpc_trace_step * 8)()
         ns = C.c_size_t()
-        _check(self.lib.gpc_trace(self.h, C.byref(soa), out.ctypes.data, lb.ctypes.data, steps, 8, C.byref(ns)),
+        _check(self.lib.gpc_trace_on(self.h, int(slot), C.byref(soa), out.ctypes.data, lb.ctypes.data, steps, 8, C.byref(ns)),
                "gpc_trace")
-        names = ("table", "verdict", "flags", "conj_id", "priority", "candidates")
-        return out, [{k: getattr(steps[i], k) for k in names} for i in range(ns.value)], lb[0]
+        return out, [{k: getattr(steps[i], k) for k in self._STEP_FIELDS} for i in range(ns.value)], lb[0]
+
+    def trace6(self, pkt: Dict[str, object], slot=0):
+        """gpc_trace6 of one IPv6 packet (dict of column values; src6 / dst6 / ct_src6 / ct_dst6: 16
+        network-order bytes, as one row of the (n, 16) columns pkt_soa_host takes) on device slot
+        `slot`: (verdicts (2,), [step dicts], lb result of LB6_DTYPE, addrs). addrs: four dicts for
+        src6, the post-DNAT dst6, ct_src6, ct_dst6 -- "prefix": the ipaddress.IPv6Network the device's
+        code stands for (None: under no prefix, or the column took no part), "code", "flags" (T6_*)."""
+        cols = {k: np.array([v], dtype=PKT_COLUMNS[k]) for k, v in pkt.items()}
+        soa, keep, n = pkt_soa_host(cols)
+        out = np.zeros(2, dtype=VERDICT_DTYPE)
+        lb = np.zeros(1, dtype=LB6_DTYPE)
+        addrs = (gpc_trace6_addr * 4)()
+        steps = (gpc_trace_step * 8)()
+        ns = C.c_size_t()
+        _check(self.lib.gpc_trace6(self.h, int(slot), C.byref(soa), out.ctypes.data, lb.ctypes.data, addrs, steps, 8,
+                                   C.byref(ns)), "gpc_trace6")
+        nets = [{"prefix": ipaddress.IPv6Network((bytes(a.prefix), a.prefix_len)) if a.prefix_len else None,
+                 "code": a.code, "flags": a.flags} for a in addrs]
+        return out, [{k: getattr(steps[i], k) for k in self._STEP_FIELDS} for i in range(ns.value)], lb[0], nets
+
+    def v6_prefix_of_code(self, code: int):
+        """gpc_debug_v6_prefix_of_code: the ipaddress.IPv6Network whose addresses the committed IPv6
+        image's LPM maps to `code` (None: the code of an address under no prefix); GpcError (EINVAL)
+        for a code that no prefix owns or without an IPv6 image. Host only."""
+        prefix = (C.c_uint8 * 16)()
+        plen = C.c_uint32()
+        _check(self.lib.gpc_debug_v6_prefix_of_code(self.h, int(code), prefix, C.byref(plen)), "gpc_debug_v6_prefix_of_code")
+        return ipaddress.IPv6Network((bytes(prefix), plen.value)) if plen.value else None
 
     def stream_epoch(self, stream: int = 0) -> int:
         """Epoch the last classify launch on `stream` was bound to (gpc_stream_epoch)."""

@@ -572,6 +572,48 @@ int gpc_classify_lb(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict
  * Endpoint, otherwise the hash choice). */
 int gpc_trace(gpc_ctx* ctx, const gpc_pkt_soa* pkt, gpc_verdict* out, gpc_lb_result* lb_out, gpc_trace_step* steps,
               size_t cap, size_t* n_steps);
+/* gpc_trace on device slot `slot` (the affinity tables are per slot: what slot k would do with the
+ * packet). gpc_trace == slot 0. A slot out of range: -GPC_EINVAL. */
+int gpc_trace_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pkt, gpc_verdict* out, gpc_lb_result* lb_out,
+                 gpc_trace_step* steps, size_t cap, size_t* n_steps);
+/* The readback of an IPv6 packet (gpc_trace6): one address column as the policy walk saw it. */
+typedef struct gpc_trace6_addr {
+  uint8_t prefix[16];            /* the interned prefix the address fell into, network order, host bits zero */
+  uint32_t prefix_len;           /* 1..128; 0 = under no prefix of the rule set (prefix all zero)             */
+  uint32_t code;                 /* the 32-bit code the device computed (what the walk matched on)           */
+  uint32_t flags;                /* GPC_T6_*                                                                 */
+  uint32_t reserved;
+} gpc_trace6_addr;
+#define GPC_T6_PRESENT 0x1       /* the column took part in the walk (else the record is all zero)            */
+#define GPC_T6_OVERFLOW 0x2      /* the code was found in a delta epoch's overflow table: the prefix was
+                                    interned by a delta commit                                              */
+#define GPC_T6_DNAT 0x4          /* addrs[1] only: the address is the Endpoint the Service stage chose        */
+/* gpc_trace for an IPv6 packet: packet 0 of the HOST columns `pkt` (src6, dst6, sport, dport, proto,
+ * out_port required; the others optional with gpc_classify6's defaults; the addresses need no
+ * alignment) through the current IPv6 epoch of device slot `slot`, exactly as gpc_classify6_lb_on
+ * runs it, in one launch: the IPv6 Service stage (when an IPv6 Service image is bound), the LPM coding
+ * of the address columns, the traced walk over the codes (base and delta epochs). out[2] and lb_out
+ * (may be NULL) equal what gpc_classify6_host_lb returns for the packet; steps as gpc_trace
+ * (-GPC_ERANGE when *n_steps > cap). addrs (4 records, may be NULL) = src6, the post-DNAT dst6,
+ * ct_src6 if given, ct_dst6 or behind a Service image the pre-NAT destination: `code` is what the
+ * device computed, `prefix` / `prefix_len` the host's translation of that code through the epoch's
+ * prefix tree (the deepest node whose code range holds it) -- not a second longest-prefix match of
+ * the address, so a wrong code shows as a prefix that does not hold the address. A code that no node
+ * of the tree owns: the outputs are filled, that record's prefix_len is 0, and the call returns
+ * -GPC_EINVAL. A Service without Endpoints: out[0] = REJECT at GPC_VTABLE_ENDPOINT_DNAT, no steps,
+ * addrs all zero. Session affinity (an IPv6 affinity Service committed, gpc_config.session_affinity6,
+ * the slot's table exists): the trace waits for the slot's pending affinity batch, then reads the
+ * table and never writes it (no claim, no bid, no entry, no counter): a live entry of the packet's
+ * key whose Endpoint still belongs to the Service gives that Endpoint (GPC_LB_AFFINITY), otherwise
+ * the packet takes its hash choice. Synchronous; debug path; holds the control-plane lock for the
+ * call (the translation reads the tree delta commits extend in place). -GPC_EINVAL without an IPv6
+ * epoch (ipv6 disabled or nothing committed), for a slot out of range or a missing required column. */
+int gpc_trace6(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pkt, gpc_verdict* out, gpc_lb_result6* lb_out,
+               gpc_trace6_addr* addrs, gpc_trace_step* steps, size_t cap, size_t* n_steps);
+/* Test hook (host only, no device): the translation gpc_trace6 applies to a code, over the committed
+ * IPv6 image's prefix tree. *prefix_len = 0 and prefix all zero: the code of an address under no
+ * prefix. -GPC_EINVAL for a code no node owns, and without an IPv6 image. */
+int gpc_debug_v6_prefix_of_code(gpc_ctx* ctx, uint32_t code, uint8_t prefix[16], uint32_t* prefix_len);
 /* IPv6 packets (pkts->src6 / dst6 columns) against the IPv6 half of the rule set (the ipv6_* /
  * tcp6 / udp6 / icmp6 flows and the family-less ones), as OVS classifies an IPv6 packet in the
  * same tables. Needs gpc_config.ipv6_enabled. A commit that changes rules publishes an IPv6 delta

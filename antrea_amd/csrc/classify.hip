@@ -4,6 +4,9 @@
 // (17 B/packet), the 16-B verdict pair is written with one 128-bit store per lane, and everything
 // else is read-only image traffic (driver bucket offsets, candidate ranks, 32-B rule records,
 // interval / box / point-hash lines) served from L2 / Infinity Cache when the image fits.
+// With counters on, the length column is read in the same round as the others and the per-rule
+// adds (memory-side atomics) are the last thing a wave issues, after its result stores: nothing
+// waits for them but the end of the wave.
 #include <hip/hip_runtime.h>
 
 #include "core.hpp"
@@ -403,6 +406,10 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
   uint32_t dest = pk.dest ? pk.dest[i] : 0u;
   const uint32_t in_port = pk.in_port ? pk.in_port[i] : 0u;
   const uint32_t tun_id = pk.tun_id ? pk.tun_id[i] : 0u;
+  // The bytes counters' packet length, in the same round (the test is wave-uniform): loaded where it
+  // is used, after the walks, it was a dependent streaming read in front of the counter adds. It is
+  // parked in the lane's LDS column below, not held in a register over a walk.
+  uint32_t len = (count && pk.len) ? uint32_t(pk.len[i]) : 0u;
   const uint32_t ct_state = pk.ct_state ? pk.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK);
   const uint32_t ct_mark = pk.ct_mark ? pk.ct_mark[i] : 0u;  // (last: its hairpin bit is tested first)
   // Service stage. kStage 0: one launch does it and both policy stages. kStage 1 / 2 (Service
@@ -492,20 +499,28 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
     lds_reload();
     return (uint64_t(i_hi) << 32) | pkt_lane[kPktWords * pkt_stride];
   };
-  auto count_one = [&](const StageOut& s, uint64_t k) {  // a stage's Metric-table counters
+  // a stage's Metric-table counters (the split launches: the length is parked in the spare word)
+  auto count_one = [&](const StageOut& s) {
     if (!count || !s.counted) return;
-    const uint32_t len = pk.len ? pk.len[k] : 0u;
+    const uint32_t len_k = pkt_lane[(kPktWords + 1) * pkt_stride];
     unsigned long long* const copy = counters + size_t(blockIdx.x & ep.ctr_mask) * ep.ctr_stride;
-    count_stage(s.v, s.slot, len, p.ax[AX_CTST], [&](uint32_t w, unsigned long long v) { atomicAdd(&copy[w], v); });
+    count_stage(s.v, s.slot, len_k, p.ax[AX_CTST], [&](uint32_t w, unsigned long long v) { atomicAdd(&copy[w], v); });
   };
   if constexpr (kStage == 0) {
     // Both stages in one launch. Nothing global happens between the two walks: the egress half
     // {conj, packed, slot | counted << 31} is parked in the lane's LDS column next to the index and
-    // the ingress bypass (nothing of it, nor of the Service stage, is held in a register over a
-    // walk), and the tail issues the len load, both stages' counter adds and then one 16-B store of
-    // the pair. (Counted and stored between the walks, the egress half's memory-side atomics and
-    // two 4-B stores stood in front of the ingress walk's first wait.)
-    pkt_lane[(kPktWords + 1) * pkt_stride] = ingress_bypass(const_hdr(ep.hdr)->isc, dest, ct_mark);
+    // the word {ingress bypass (bits 0-8), len << 16} (nothing of them, nor of the Service stage, is
+    // held in a register over a walk). (Counted and stored between the walks, the egress half's
+    // memory-side atomics and two 4-B stores stood in front of the ingress walk's first wait.)
+    // The tail issues the result store(s) and then both stages' counter adds, and ends: nothing
+    // waits for an add. (Adds first, the store stood behind the wait for every add's
+    // acknowledgement -- the join with the grouped path's orig[k] load waits for vmcnt(0), one
+    // in-order counter -- and the adds behind the len load: three latencies in series.) A grouped
+    // batch without the un-permute loads orig[k] before the store, so before any add.
+    // (len is made opaque here: its shift, moved up into the load's wave-uniform branch, waited for
+    // the load in the middle of the round of column loads.)
+    asm volatile("" : "+v"(len));
+    pkt_lane[(kPktWords + 1) * pkt_stride] = ingress_bypass(const_hdr(ep.hdr)->isc, dest, ct_mark) | (len << 16);
     uint32_t a1;
     {
       const StageOut s1 = walk_stage<kDelta, false>(im, p, 1u, nullptr, nullptr);
@@ -519,7 +534,7 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
     s2.v.conj = s2.v.packed = s2.slot = 0u;
     s2.counted = 0;
     if (a1 != RV_DROP && a1 != RV_REJECT && a1 != RV_ISO_DROP) {
-      if (const uint32_t byp = pkt_lane[(kPktWords + 1) * pkt_stride]) {  // IngressSecurityClassifier
+      if (const uint32_t byp = pkt_lane[(kPktWords + 1) * pkt_stride] & 0xffffu) {  // IngressSecurityClassifier
         s2.v.packed = pack_verdict(byp & 0xffu, 0, 0, (byp >> 8) ? 2u : 0u);
       } else {
         s2 = walk_stage<kDelta, false>(im, p, 4u, nullptr, nullptr);
@@ -532,29 +547,32 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
     const uint32_t es = pkt_lane[(kPktWords + 4) * pkt_stride];
     s1.slot = es & ~kParkCounted;
     s1.counted = (es & kParkCounted) != 0u;
-    if (count && (s1.counted || s2.counted)) {  // the Metric tables' counters of both stages
-      const uint32_t len = pk.len ? pk.len[k] : 0u;
-      const uint32_t cts = p.ax[AX_CTST];
-      unsigned long long* const copy = counters + size_t(blockIdx.x & ep.ctr_mask) * ep.ctr_stride;
-      auto add = [&](uint32_t w, unsigned long long v) { atomicAdd(&copy[w], v); };
-      if (s1.counted) count_stage(s1.v, s1.slot, len, cts, add);
-      if (s2.counted) count_stage(s2.v, s2.slot, len, cts, add);
-    }
     if (gout) {  // grouped order (un-permuted afterwards)
       mid[k] = make_uint2(s1.v.conj, s1.v.packed);
       gout[k] = make_uint2(s2.v.conj, s2.v.packed);
     } else {
       out[at(k)] = make_uint4(s1.v.conj, s1.v.packed, s2.v.conj, s2.v.packed);
     }
+    if (count && (s1.counted || s2.counted)) {  // the Metric tables' counters of both stages
+      const uint32_t len_k = pkt_lane[(kPktWords + 1) * pkt_stride] >> 16;
+      const uint32_t cts = p.ax[AX_CTST];
+      unsigned long long* const copy = counters + size_t(blockIdx.x & ep.ctr_mask) * ep.ctr_stride;
+      auto add = [&](uint32_t w, unsigned long long v) { atomicAdd(&copy[w], v); };
+      if (s1.counted) count_stage(s1.v, s1.slot, len_k, cts, add);
+      if (s2.counted) count_stage(s2.v, s2.slot, len_k, cts, add);
+    }
     return;
   }
+  // The split launches: the same order -- the length parked, the result stored (store2's loads of
+  // mid[k] / orig[k] come before it), then the stage's adds and the end.
+  pkt_lane[(kPktWords + 1) * pkt_stride] = len;
   const StageOut s = walk_stage<kDelta, false>(im, p, kStage == 2 ? 4u : 1u, nullptr, nullptr);
   const uint64_t il = late();
-  count_one(s, il);
   const VerdictOut e = s.v, g = s.v;
   if (kStage == 2) store2(il, g.conj, g.packed);
   else if (kStage == 1 && mid) mid[il] = make_uint2(e.conj, e.packed);
   else out[il] = make_uint4(e.conj, e.packed, 0u, 0u);  // ingress NONE until the second launch
+  count_one(s);
 }
 
 // kDelta: the epoch mode (core.hpp kModeBase / kModeExt / kModeJournal).

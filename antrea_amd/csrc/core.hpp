@@ -1586,7 +1586,11 @@ GPC_HD TablePart eval_part(const Img& im, uint32_t table, const Pkt& p) {
       if (uint32_t(i) < nc) {
         const CSubIdx& si = th.cidx[i];
         bk[i] = cbucket_of(si_band(si), si_bits(si), key[i], xv);
-        if (si.pres) {
+        // (a combination sub-index keeps its membership hash at `pres` and has no presence map;
+        // combination 0 lists nothing)
+        if (si_band(si) == kBandCombo) {
+          pw[i] = key[i] != 0u ? ~0u : 0u;
+        } else if (si.pres) {
           GPC_TOUCH(im.blob + si.pres + (bk[i] >> 5), 4);
           pw[i] = im.blob[si.pres + (bk[i] >> 5)];
         } else {

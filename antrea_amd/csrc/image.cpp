@@ -1159,6 +1159,12 @@ constexpr uint64_t kMergeMinBytes = uint64_t(16) << 20;
 // kComboMax combinations (ids fit the entries' 16 spare bits).
 constexpr uint64_t kComboMinEntries = 1u << 16;
 constexpr size_t kComboMax = 65535;
+// GPC_COMBO_MIN_ENTRIES overrides the entry threshold (tests: small rule sets that reach the format);
+// read at every build, like GPC_COMPOSITE
+uint64_t combo_min_entries() {
+  const char* e = std::getenv("GPC_COMBO_MIN_ENTRIES");
+  return e && *e ? std::strtoull(e, nullptr, 10) : kComboMinEntries;
+}
 // Membership hash of a combination sub-index (core.hpp combo_of): {lg, 0, 0, 0}, then 2^lg buckets
 // of two {host value, combination id} slots, two choices, load <= 1/2 (combination 0: empty slot).
 uint32_t put_combo_members(const std::vector<std::pair<uint32_t, uint32_t>>& members, Blob& B, HostImage* out) {
@@ -1396,7 +1402,7 @@ void build_composite(const std::vector<RuleB*>& rs, const std::vector<uint32_t>&
                                   iv.first, iv.second});
           skips[e.xi] = skip;
         }
-        if (!elig || old_n < kComboMinEntries) continue;
+        if (!elig || old_n < combo_min_entries()) continue;
         std::map<std::vector<uint32_t>, uint32_t> set_ids;
         std::vector<std::vector<uint32_t>> set_rules;  // set id -> rules (xi)
         for (auto& h : hosts) {
@@ -1561,7 +1567,8 @@ void build_composite(const std::vector<RuleB*>& rs, const std::vector<uint32_t>&
       // is always in the map) with >= 2 sub-indexes. With an IP value axis (egress: the Pod IPs) the
       // map already drops most packets, and the bitmaps only take L2 room: C3 egress 3.57 -> 3.98 ms
       // with them, ingress 5.56 -> 5.01 ms; C2 (one sub-index) unchanged (profiles/r04g_*).
-      const bool want_pres = X > AX_CTDST && sub.size() >= 2;
+      // (not for a combination sub-index: `pres` holds its membership hash)
+      const bool want_pres = X > AX_CTDST && sub.size() >= 2 && !combo;
       if (want_pres && !std::getenv("GPC_NO_PRESENCE")) {  // (GPC_NO_PRESENCE: experiments)
         std::vector<uint32_t> pres(nb / 32, 0u);
         for (uint32_t b = 0; b < nb; b++)

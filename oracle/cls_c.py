@@ -66,13 +66,26 @@ def _verdict_sig(actions) -> int:
     return zlib.crc32(repr(sig).encode())
 
 
-def _convert_lines(flow_lines: List[str]):
-    """Flow text -> (flow records, action records, index of each kept flow in flow_lines)."""
+def _convert_lines(flow_lines: List[str], cache: Optional[dict] = None):
+    """Flow text -> (flow records, action records, index of each kept flow in flow_lines).
+    `cache`: {line: (record, its action records) or None for a dropped line}, filled and used here --
+    callers that convert a slowly changing dump again and again parse only the new lines."""
     flows = np.zeros(len(flow_lines), FLOW_DT)
     acts = []
     kept = []
     k = 0
     for li, line in enumerate(flow_lines):
+        if cache is not None and line in cache:
+            hit = cache[line]
+            if hit is not None:
+                flows[k] = hit[0]
+                flows[k]["act_off"] = len(acts)
+                acts.extend(hit[1])
+                kept.append(li)
+                k += 1
+            continue
+        if cache is not None:
+            cache[line] = None
         f = parse_flow(line)
         t = TABLE_IDS.get(f["table"], 0)
         if t not in KEEP_TABLES:
@@ -129,6 +142,8 @@ def _convert_lines(flow_lines: List[str]):
         rec["n_act"] = len(acts) - off
         rec["soft"] = int(soft)
         rec["sig"] = 0 if soft else _verdict_sig(f["actions"])
+        if cache is not None:
+            cache[line] = (rec.copy(), acts[off:])
         kept.append(li)
         k += 1
     return flows[:k].copy(), np.array(acts, dtype=ACT_DT) if acts else np.zeros(0, ACT_DT), kept
@@ -140,12 +155,12 @@ def _convert_chunk(args):
     return fl, ac, [base + i for i in kept]
 
 
-def _convert(flow_lines: List[str], procs: Optional[int] = None):
+def _convert(flow_lines: List[str], procs: Optional[int] = None, cache: Optional[dict] = None):
     """Parallel conversion of large dumps (a fork pool over chunks; the oracle never touches a GPU)."""
     n = len(flow_lines)
     procs = procs if procs is not None else min(16, os.cpu_count() or 1)
-    if n < 50000 or procs <= 1:
-        return _convert_lines(flow_lines)
+    if n < 50000 or procs <= 1 or cache is not None:
+        return _convert_lines(flow_lines, cache)
     import multiprocessing as mp
     step = (n + 4 * procs - 1) // (4 * procs)
     chunks = [(flow_lines[i:i + step], i) for i in range(0, n, step)]
@@ -165,10 +180,11 @@ def _convert(flow_lines: List[str], procs: Optional[int] = None):
 
 
 class CPipeline:
-    def __init__(self, flow_lines: List[str], tiers: Optional[Dict[int, int]] = None, procs: Optional[int] = None):
+    def __init__(self, flow_lines: List[str], tiers: Optional[Dict[int, int]] = None, procs: Optional[int] = None,
+                 cache: Optional[dict] = None):
         lib = load()
         flow_lines = list(flow_lines)
-        flows, acts, kept = _convert(flow_lines, procs)
+        flows, acts, kept = _convert(flow_lines, procs, cache)
         self._flows = np.ascontiguousarray(flows, dtype=FLOW_DT)
         self._acts = np.ascontiguousarray(acts, dtype=ACT_DT)
         assert self._flows.dtype.itemsize == 184 and self._acts.dtype.itemsize == 32

@@ -233,3 +233,73 @@ extern "C" int emu_classify6(const uint32_t* blob, const void* hdr, const uint32
   }
   return 0;
 }
+
+// What build_composite laid out (host image of a classifier): per table t (0..5) the composite
+// sub-indexes as {axis, band, fmt, bits, longest bucket list} in info[t][i][5], their number in n_sub[t].
+extern "C" int emu_composite_info(const uint32_t* blob, const void* hdr, uint32_t* info, uint32_t* n_sub) {
+  const ImageHdr* h = static_cast<const ImageHdr*>(hdr);
+  for (int t = 0; t < 6; t++) {
+    const TableHdr& th = h->t[t];
+    n_sub[t] = th.n_cidx;
+    for (uint32_t i = 0; i < th.n_cidx && i < uint32_t(kIdxPerClause); i++) {
+      const SubIdx& si = th.cidx[i];
+      uint32_t longest = 0;
+      for (uint32_t b = 0; b < (1u << si.bits); b++) longest = std::max(longest, sub_bucket_len(blob, si, b));
+      uint32_t* o = info + 5 * (kIdxPerClause * t + i);
+      o[0] = si.axis, o[1] = si.band, o[2] = si.fmt, o[3] = si.bits, o[4] = longest;
+    }
+  }
+  return 0;
+}
+
+// combo_of over n host values for sub-index i of table t (0..5), which must have band kBandCombo.
+extern "C" int emu_combo_ids(const uint32_t* blob, const void* hdr, uint32_t t, uint32_t i, const uint32_t* vals, size_t n,
+                             uint32_t* ids) {
+  const ImageHdr* h = static_cast<const ImageHdr*>(hdr);
+  if (t >= 6 || i >= h->t[t].n_cidx || h->t[t].cidx[i].band != kBandCombo) return -1;
+  for (size_t k = 0; k < n; k++) ids[k] = combo_of(blob, h->t[t].cidx[i].pres, vals[k]);
+  return 0;
+}
+
+// Every entry of combination sub-index i of table t (0..5), read through its buckets, against
+// entry_pass: a packet that holds the entry's value and the low end of its interval passes with the
+// entry's own combination id as cp and with no other. out = {entries, entries with an id above 255,
+// passes with the id, passes with the id's bit 8 flipped, passes with its bit 0 flipped, passes with 0}.
+extern "C" int emu_combo_entry_check(const uint32_t* blob, const void* hdr, uint32_t t, uint32_t i, unsigned long long* out) {
+  const ImageHdr* h = static_cast<const ImageHdr*>(hdr);
+  if (t >= 6 || i >= h->t[t].n_cidx || h->t[t].cidx[i].band != kBandCombo) return -1;
+  const SubIdx& si = h->t[t].cidx[i];
+  const Ent* E = reinterpret_cast<const Ent*>(blob);
+  for (int k = 0; k < 6; k++) out[k] = 0;
+  for (uint32_t b = 0; b < (1u << si.bits); b++) {
+    uint32_t lo, hi;
+    if (si.fmt) {
+      dir_list(blob, si, b, &lo, &hi);
+      if (hi - lo == kDirCountMax) {
+        const Ent pe = E[lo];
+        lo = si.ent / 4u + pe.y;
+        hi = lo + pe.lo;
+      }
+    } else {
+      lo = si.ent / 4u + blob[si.off + b];
+      hi = si.ent / 4u + blob[si.off + b + 1];
+    }
+    g_lines.clear();
+    g_line_site.clear();
+    for (uint32_t j = lo; j < hi; j++) {
+      const Ent e = E[j];
+      if ((e.x & 15u) != kFiltCombo || !(e.x & kEntExactX)) return -2;  // not a combination entry
+      const uint32_t id = (e.lo >> 24) | ((e.hi >> 24) << 8), iax = (e.x >> 4) & 15u;
+      uint32_t pst[kPktWords] = {0};
+      Pkt p(pst, 1);
+      if (iax < AX_N) p.ax[iax] = e.lo & 0xffffffu;
+      out[0]++;
+      out[1] += id > 255u;
+      out[2] += entry_pass(p, e, e.y, id);
+      out[3] += entry_pass(p, e, e.y, id ^ 0x100u);
+      out[4] += entry_pass(p, e, e.y, id ^ 1u);
+      out[5] += entry_pass(p, e, e.y, 0u);
+    }
+  }
+  return 0;
+}

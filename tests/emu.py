@@ -38,7 +38,56 @@ def load():
     _lib.emu_classify6.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(gpc.gpc_pkt_soa),
                                    C.c_size_t, C.c_void_p, C.c_void_p]
     _lib.emu_v6_codes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    _lib.emu_composite_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _lib.emu_combo_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+    _lib.emu_combo_entry_check.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     return _lib
+
+
+TABLES = ("AntreaPolicyEgressRule", "EgressRule", "EgressDefaultRule", "AntreaPolicyIngressRule", "IngressRule",
+          "IngressDefaultRule")  # core.hpp ImageHdr.t
+BAND_COMBO = 5  # core.hpp kBandCombo
+DIR_COUNT_MAX = 7  # core.hpp kDirCountMax
+
+
+def composite_layout(clf: "gpc.Classifier"):
+    """{table name: [{"axis", "band", "fmt", "bits", "longest"}]}: the composite sub-indexes of the
+    host image last committed by clf (image.cpp build_composite), `longest` the longest bucket list."""
+    blob, nw, hdr, _ = clf.debug_image()
+    info, n_sub = np.zeros((6, 5, 5), np.uint32), np.zeros(6, np.uint32)
+    load().emu_composite_info(blob, hdr, info.ctypes.data, n_sub.ctypes.data)
+    names = ("axis", "band", "fmt", "bits", "longest")
+    return {TABLES[t]: [dict(zip(names, (int(x) for x in info[t, i]))) for i in range(int(n_sub[t]))] for t in range(6)}
+
+
+def combo_ids(clf: "gpc.Classifier", table, values):
+    """core.hpp combo_of of the host values (uint32 addresses) in `table`'s combination sub-index:
+    (n,) uint32 ids, 0 = in no host set. Asserts that the table has such a sub-index."""
+    t = TABLES.index(table)
+    subs = composite_layout(clf)[table]
+    idx = [i for i, s in enumerate(subs) if s["band"] == BAND_COMBO]
+    assert len(idx) == 1, "%s: no combination sub-index (%s)" % (table, subs)
+    blob, nw, hdr, _ = clf.debug_image()
+    v = np.ascontiguousarray(values, dtype=np.uint32)
+    ids = np.zeros(len(v), np.uint32)
+    rc = load().emu_combo_ids(blob, hdr, t, idx[0], v.ctypes.data, len(v), ids.ctypes.data)
+    assert rc == 0
+    return ids
+
+
+def combo_entry_check(clf: "gpc.Classifier", table):
+    """Every entry of `table`'s combination sub-index through core.hpp entry_pass, with a packet that
+    holds the entry's value and interval: {"entries", "id_above_255", "pass_own_id", "pass_bit8_flipped",
+    "pass_bit0_flipped", "pass_id0"} (counts)."""
+    t = TABLES.index(table)
+    idx = [i for i, s in enumerate(composite_layout(clf)[table]) if s["band"] == BAND_COMBO]
+    assert len(idx) == 1, "%s: no combination sub-index" % table
+    blob, nw, hdr, _ = clf.debug_image()
+    out = (C.c_ulonglong * 6)()
+    rc = load().emu_combo_entry_check(blob, hdr, t, idx[0], out)
+    assert rc == 0, rc
+    return dict(zip(("entries", "id_above_255", "pass_own_id", "pass_bit8_flipped", "pass_bit0_flipped", "pass_id0"),
+                    (int(x) for x in out)))
 
 
 def v6_codes(clf: "gpc.Classifier", addrs):
@@ -128,6 +177,11 @@ def stats(reset=False):
         for i in range(16):
             arr[i] = 0
     return v
+
+
+def pkt_scan(n):
+    """Driver-index entries the last classify() scanned for each of its first n packets (both stages)."""
+    return np.array((C.c_uint * (1 << 20)).in_dll(load(), "gpc_emu_pkt_scan")[:n], np.uint32)
 
 
 def site_lines(reset=False):

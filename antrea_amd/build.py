@@ -31,7 +31,7 @@ if ARCH != "gfx950":  # the grouping / un-permute kernels use up to 141 KB of LD
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 HOST_SRCS = ["compiler.cpp", "image.cpp", "flowtext.cpp", "service.cpp"]
-HIP_SRCS = ["classify.hip", "api.cpp"]
+HIP_SRCS = ["classify.hip", "packetin.hip", "api.cpp"]
 HEADERS = ["model.hpp", "compiler.hpp", "core.hpp", "image.hpp", "launch.hpp", "oplog.hpp", "service.hpp"]
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 

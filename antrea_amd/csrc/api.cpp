@@ -117,6 +117,7 @@ struct DevEpoch {
   int jmode = kModeBase;                // what the kernel reads of it (Journal::mode: point extensions only, or the journal)
   std::shared_ptr<DevImage> svc;        // Service image (d_hdr unused), shared until Services change
   std::shared_ptr<DevImage> svc6;       // IPv6 Service image, under the same rules
+  std::shared_ptr<DevImage> pin;        // packet-in image (d_hdr unused; null: none), shared until it changes
   std::shared_ptr<DevImage> v6;         // IPv6 base image (ipv6_enabled), shared by its delta epochs
   std::shared_ptr<DevImage> v6_pool;    // journal pool of that base (append-only)
   uint32_t v6_jhdr = 0;                 // this epoch's IPv6 JournalHdr (0: base only)
@@ -247,6 +248,12 @@ struct gpc_ctx {
   std::vector<uint32_t> svc_blob;        // host copy of the Service image (empty: no Services)
   std::vector<uint32_t> svc6_blob;       // host copy of the IPv6 Service image (empty: no IPv6 Services)
   uint64_t svc_gen = ~0ull;              // FeatureService generation the image was built from
+  // Packet-in image (core.hpp PinHdr): host copy (empty: no flow loads PacketInOperationField), the
+  // map it was built from and the FeatureNP::pin_generation() seen last
+  std::vector<uint32_t> pin_blob;
+  std::map<uint32_t, uint32_t> pin_map;
+  uint64_t pin_gen = 0;
+  bool pin_unpublished = false;          // pin_blob changed and no commit has put it on the device slots yet
   SlotMap slots;
   HostImage last;    // base image of the current epoch: shadow state for re-upload + debug export
   HostImage last6;   // IPv6 base image (ipv6_enabled)
@@ -516,6 +523,42 @@ static int upload_words(const std::vector<uint32_t>& w, int device, hipStream_t 
 
 static bool svc_has_affinity(const std::vector<uint32_t>& blob) {
   return blob.size() * 4 >= sizeof(SvcHdr) && reinterpret_cast<const SvcHdr*>(blob.data())->n_aff != 0;
+}
+
+// The packet-in image (core.hpp PinHdr) of conj id -> PacketInOperationField; empty map: no image.
+// Each id goes to the emptier of its two buckets; the table doubles until every id has a slot.
+static std::vector<uint32_t> build_pin_image(const std::map<uint32_t, uint32_t>& ops) {
+  std::vector<uint32_t> blob;
+  if (ops.empty()) return blob;
+  const size_t n = ops.size();
+  uint32_t map_log2 = 5, hash_log2 = 0;
+  while ((size_t(1) << map_log2) < 16 * n) map_log2++;
+  while ((size_t(kPinSlots) << hash_log2) < 2 * n) hash_log2++;
+  for (;; hash_log2++) {
+    const uint32_t mask = (1u << hash_log2) - 1u;
+    const size_t map_words = size_t(1) << (map_log2 - 5), hash_off = kPinHdrWords + map_words;
+    blob.assign(hash_off + (size_t(kPinBucketWords) << hash_log2), 0u);
+    PinHdr h{uint32_t(n), kPinHdrWords, map_log2, uint32_t(hash_off), hash_log2, {0, 0, 0}};
+    std::memcpy(blob.data(), &h, sizeof h);
+    bool ok = true;
+    for (auto& kv : ops) {
+      const uint32_t mb = pin_map_bit(kv.first, map_log2);
+      blob[kPinHdrWords + (mb >> 5)] |= 1u << (mb & 31u);
+      uint32_t* b[2] = {&blob[hash_off + size_t(pin_b1(kv.first, mask)) * kPinBucketWords],
+                        &blob[hash_off + size_t(pin_b2(kv.first, mask)) * kPinBucketWords]};
+      uint32_t used[2] = {0, 0};
+      for (int c = 0; c < 2; c++)
+        while (used[c] < kPinSlots && b[c][2 * used[c]]) used[c]++;
+      const int c = used[1] < used[0] ? 1 : 0;
+      if (used[c] == kPinSlots) {
+        ok = false;
+        break;
+      }
+      b[c][2 * used[c]] = kv.first;
+      b[c][2 * used[c] + 1] = kv.second;
+    }
+    if (ok) return blob;
+  }
 }
 
 static void collect_retired(DevState& D, bool wait) {  // the slot's device is current
@@ -1164,6 +1207,7 @@ int gpc_replay(gpc_ctx* ctx) {
     if (!rc && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
     if (!rc && !ctx->svc6_blob.empty()) rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6);
     if (!rc && ne[k].svc6) ne[k].svc6->affinity = svc_has_affinity(ctx->svc6_blob);
+    if (!rc && !ctx->pin_blob.empty()) rc = upload_words(ctx->pin_blob, D.device, us, &ne[k].pin);
     if (!rc && (hip_ok(hipMalloc(&nc[k], cap * kCounterBytes * (copies + 1))) ||
                 hip_ok(hipMemset(nc[k], 0, cap * kCounterBytes * (copies + 1)))))
       rc = -GPC_EDEV;
@@ -1179,6 +1223,7 @@ int gpc_replay(gpc_ctx* ctx) {
   }
   if (jn.active()) jn.uploaded = jn.pool.size();
   if (ctx->journal6.active()) ctx->journal6.uploaded = ctx->journal6.pool.size();
+  ctx->pin_unpublished = false;
   const uint64_t epoch = ++ctx->epoch;
   PublishLock d(ctx->data, ctx->publishers);
   for (size_t k = 0; k < ctx->dev.size(); k++) {
@@ -1558,10 +1603,30 @@ static int note_launch(gpc_ctx* ctx, DevState& D, hipStream_t st) {
   return hip_ok(hipEventRecord(ev, st));
 }
 
-int gpc_classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
-                    gpc_lb_result* lb_out, int32_t count, void* stream) {
+// A packet-in queue as gpc_classify*_pin_on take it, for a batch of n packets.
+static int pin_queue_check(const gpc_pin_queue* q, size_t n) {
+  if (!q || !q->count || (q->cap && !q->records)) return -GPC_EINVAL;
+  if (reinterpret_cast<uintptr_t>(q->records) % 16 || reinterpret_cast<uintptr_t>(q->scratch) % 16 ||
+      reinterpret_cast<uintptr_t>(q->count) % 8)
+    return -GPC_EINVAL;
+  if (n && (!q->scratch || q->scratch_bytes < pin_scratch_bytes(n))) return -GPC_EINVAL;
+  return GPC_OK;
+}
+// The collection behind the classify launches of one call (ctx->data held: the image is the one of
+// the epoch the verdicts came from). n == 0: the count alone.
+static int pin_collect(const DevState& D, const gpc_pin_queue* q, const gpc_verdict* out, size_t n, hipStream_t st,
+                       LaunchMarks* marks) {
+  if (n == 0) return hip_ok(hipMemsetAsync(q->count, 0, sizeof(uint64_t), st));
+  return launch_pin(D.cur.pin ? D.cur.pin->d_blob : nullptr, out, n, q->records, q->cap,
+                    reinterpret_cast<unsigned long long*>(q->count), q->scratch, st, marks);
+}
+
+// gpc_classify_on, with an optional packet-in queue (null: exactly the launches of a call without one).
+static int classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result* lb_out,
+                       const gpc_pin_queue* q, int32_t count, void* stream) {
   if (!ctx || !pk || (!out && n) || n > GPC_MAX_BATCH || slot >= ctx->dev.size()) return -GPC_EINVAL;
   if (n && (!pk->src || !pk->dst || !pk->sport || !pk->dport || !pk->proto || !pk->out_port)) return -GPC_EINVAL;
+  if (q && pin_queue_check(q, n)) return -GPC_EINVAL;
   if (hip_ok(hipSetDevice(ctx->dev[slot].device))) return -GPC_EDEV;
   Pace pace(ctx, slot, (hipStream_t)stream, n != 0);
   const auto d = launch_lock(ctx->data, ctx->publishers);
@@ -1604,22 +1669,40 @@ int gpc_classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n
     scratch = nullptr;  // a performance choice, never a data-path failure
   }
   int rc;
+  LaunchMarks* const marks = n ? next_marks(D) : nullptr;
   if (affinity) {
     AffLaunch al;
-    LaunchMarks* marks = next_marks(D);
     if ((rc = aff_prepare(ctx, D, st, marks, &al))) return rc;
     al.lb_scratch = scratch;
     rc = launch_classify_aff(ep, *pk, n, out, reinterpret_cast<uint4*>(lb_out), D.d_counters, count,
                              ga.scratch ? &ga : nullptr, st, marks, al);
   } else {
     rc = launch_classify(ep, *pk, n, out, reinterpret_cast<uint4*>(lb_out), D.d_counters, count,
-                         ga.scratch ? &ga : nullptr, st, n ? next_marks(D) : nullptr,
+                         ga.scratch ? &ga : nullptr, st, marks,
                          park_bytes && scratch ? reinterpret_cast<uint4*>(scratch) : nullptr);
   }
   if (!rc && scratch) rc = group_scratch_used(D, st);
+  if (!rc && q) rc = pin_collect(D, q, out, n, st, marks);
   if (rc || n == 0) return rc;
   pace.record();
   return note_launch(ctx, D, st);
+}
+
+int gpc_classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
+                    gpc_lb_result* lb_out, int32_t count, void* stream) {
+  return classify_on(ctx, slot, pk, n, out, lb_out, nullptr, count, stream);
+}
+
+int gpc_classify_pin_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
+                        gpc_lb_result* lb_out, const gpc_pin_queue* q, int32_t count, void* stream) {
+  if (!q) return -GPC_EINVAL;
+  return classify_on(ctx, slot, pk, n, out, lb_out, q, count, stream);
+}
+
+int gpc_pin_scratch_bytes(size_t n, size_t* bytes) {
+  if (!bytes || n > GPC_MAX_BATCH) return -GPC_EINVAL;
+  *bytes = size_t(pin_scratch_bytes(n));
+  return GPC_OK;
 }
 
 int gpc_trace(gpc_ctx* ctx, const gpc_pkt_soa* pk, gpc_verdict* out, gpc_lb_result* lb_out, gpc_trace_step* steps,
@@ -1829,10 +1912,12 @@ int gpc_classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t 
   return gpc_classify6_lb_on(ctx, slot, pk, n, out, nullptr, count, stream);
 }
 
-int gpc_classify6_lb_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
-                        gpc_lb_result6* lb_out, int32_t count, void* stream) {
+// gpc_classify6_lb_on, with an optional packet-in queue (null: exactly the launches of a call without one).
+static int classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
+                        const gpc_pin_queue* q, int32_t count, void* stream) {
   static_assert(sizeof(gpc_lb_result6) == 32, "two 128-bit stores per packet (classify.hip v6_lb_kernel)");
   if (reinterpret_cast<uintptr_t>(lb_out) % 16) return -GPC_EINVAL;
+  if (q && pin_queue_check(q, n)) return -GPC_EINVAL;
   if (!ctx || !pk || (!out && n) || n > GPC_MAX_BATCH || slot >= ctx->dev.size()) return -GPC_EINVAL;
   if (n && (!pk->src6 || !pk->dst6 || !pk->sport || !pk->dport || !pk->proto || !pk->out_port)) return -GPC_EINVAL;
   for (const void* c : {(const void*)pk->src6, (const void*)pk->dst6, (const void*)pk->ct_src6, (const void*)pk->ct_dst6})
@@ -1884,20 +1969,67 @@ int gpc_classify6_lb_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size
                             svc6 && scratch ? scratch + code_words : nullptr, reinterpret_cast<uint4*>(lb_out),
                             affinity6 ? &al : nullptr);
   if (!rc && scratch) rc = group_scratch_used(D, st);
+  if (!rc && q) rc = pin_collect(D, q, out, n, st, marks);
   if (rc || n == 0) return rc;
   pace.record();
   return note_launch(ctx, D, st);
+}
+
+int gpc_classify6_lb_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
+                        gpc_lb_result6* lb_out, int32_t count, void* stream) {
+  return classify6_on(ctx, slot, pk, n, out, lb_out, nullptr, count, stream);
+}
+
+int gpc_classify6_pin_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
+                         gpc_lb_result6* lb_out, const gpc_pin_queue* q, int32_t count, void* stream) {
+  if (!q) return -GPC_EINVAL;
+  return classify6_on(ctx, slot, pk, n, out, lb_out, q, count, stream);
 }
 
 int gpc_classify6_host(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, int32_t count) {
   return gpc_classify6_host_lb(ctx, pk, n, out, nullptr, count);
 }
 
-int gpc_classify6_host_lb(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
+// Device buffers of the packet-in queue of a synchronous host call (gpc_classify*_host_pin*).
+struct HostPin {
+  gpc_packet_in* recs;  // host, cap entries (null: cap == 0)
+  size_t cap;
+  uint64_t* total;
+  gpc_pin_queue q{};
+  int alloc(size_t n) {
+    size_t sb = 0;
+    if (gpc_pin_scratch_bytes(n, &sb)) return -GPC_EINVAL;
+    q.cap = cap;
+    q.scratch_bytes = sb;
+    if ((cap && hip_ok(hipMalloc((void**)&q.records, cap * sizeof(gpc_packet_in)))) || hip_ok(hipMalloc((void**)&q.count, 8)) ||
+        (sb && hip_ok(hipMalloc(&q.scratch, sb))))
+      return -GPC_EDEV;
+    return GPC_OK;
+  }
+  int fetch() {  // the device is synchronized
+    uint64_t t = 0;
+    if (hip_ok(hipMemcpy(&t, q.count, 8, hipMemcpyDeviceToHost))) return -GPC_EDEV;
+    const size_t k = size_t(std::min<uint64_t>(t, cap));
+    if (k && hip_ok(hipMemcpy(recs, q.records, k * sizeof(gpc_packet_in), hipMemcpyDeviceToHost))) return -GPC_EDEV;
+    *total = t;
+    return GPC_OK;
+  }
+  ~HostPin() {
+    if (q.records) (void)hipFree(q.records);
+    if (q.count) (void)hipFree(q.count);
+    if (q.scratch) (void)hipFree(q.scratch);
+  }
+};
+
+static int classify6_host(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out, HostPin* hp,
                           int32_t count) {
   if (!ctx || !pk || (!out && n)) return -GPC_EINVAL;
+  if (hp && (!hp->total || (hp->cap && !hp->recs))) return -GPC_EINVAL;
   if (hip_ok(hipSetDevice(ctx->dev[0].device))) return -GPC_EDEV;
-  if (n == 0) return GPC_OK;
+  if (n == 0) {
+    if (hp) *hp->total = 0;
+    return GPC_OK;
+  }
   gpc_pkt_soa d{};
   std::vector<void*> allocs;
   int rc = GPC_OK;
@@ -1931,14 +2063,27 @@ int gpc_classify6_host_lb(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_ver
   void* dlb = nullptr;
   if (!rc && hip_ok(hipMalloc(&dout, n * 2 * sizeof(gpc_verdict)))) rc = -GPC_EDEV;
   if (!rc && lb_out && hip_ok(hipMalloc(&dlb, n * sizeof(gpc_lb_result6)))) rc = -GPC_EDEV;
-  if (!rc) rc = gpc_classify6_lb(ctx, &d, n, (gpc_verdict*)dout, (gpc_lb_result6*)dlb, count, nullptr);
+  if (!rc && hp) rc = hp->alloc(n);
+  if (!rc) rc = classify6_on(ctx, 0, &d, n, (gpc_verdict*)dout, (gpc_lb_result6*)dlb, hp ? &hp->q : nullptr, count, nullptr);
   if (!rc && hip_ok(hipDeviceSynchronize())) rc = -GPC_EDEV;
   if (!rc && hip_ok(hipMemcpy(out, dout, n * 2 * sizeof(gpc_verdict), hipMemcpyDeviceToHost))) rc = -GPC_EDEV;
   if (!rc && lb_out && hip_ok(hipMemcpy(lb_out, dlb, n * sizeof(gpc_lb_result6), hipMemcpyDeviceToHost))) rc = -GPC_EDEV;
+  if (!rc && hp) rc = hp->fetch();
   if (dout) (void)hipFree(dout);
   if (dlb) (void)hipFree(dlb);
   for (void* p : allocs) (void)hipFree(p);
   return rc;
+}
+
+int gpc_classify6_host_lb(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
+                          int32_t count) {
+  return classify6_host(ctx, pk, n, out, lb_out, nullptr, count);
+}
+
+int gpc_classify6_host_pin(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
+                           gpc_packet_in* recs, size_t cap, uint64_t* total, int32_t count) {
+  HostPin hp{recs, cap, total};
+  return classify6_host(ctx, pk, n, out, lb_out, &hp, count);
 }
 
 int gpc_classify_host_lb(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result* lb_out,
@@ -1946,11 +2091,15 @@ int gpc_classify_host_lb(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verd
   return gpc_classify_host_on(ctx, 0, pk, n, out, lb_out, count);
 }
 
-int gpc_classify_host_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
-                         gpc_lb_result* lb_out, int32_t count) {
+static int classify_host(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result* lb_out,
+                         HostPin* hp, int32_t count) {
   if (!ctx || !pk || (!out && n) || slot >= ctx->dev.size()) return -GPC_EINVAL;
+  if (hp && (!hp->total || (hp->cap && !hp->recs))) return -GPC_EINVAL;
   if (hip_ok(hipSetDevice(ctx->dev[slot].device))) return -GPC_EDEV;
-  if (n == 0) return GPC_OK;
+  if (n == 0) {
+    if (hp) *hp->total = 0;
+    return GPC_OK;
+  }
   gpc_pkt_soa d{};
   std::vector<void*> allocs;
   int rc = GPC_OK;
@@ -1984,14 +2133,27 @@ int gpc_classify_host_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, siz
   void* dlb = nullptr;
   if (!rc && hip_ok(hipMalloc(&dout, n * 2 * sizeof(gpc_verdict)))) rc = -GPC_EDEV;
   if (!rc && lb_out && hip_ok(hipMalloc(&dlb, n * sizeof(gpc_lb_result)))) rc = -GPC_EDEV;
-  if (!rc) rc = gpc_classify_on(ctx, slot, &d, n, (gpc_verdict*)dout, (gpc_lb_result*)dlb, count, nullptr);
+  if (!rc && hp) rc = hp->alloc(n);
+  if (!rc) rc = classify_on(ctx, slot, &d, n, (gpc_verdict*)dout, (gpc_lb_result*)dlb, hp ? &hp->q : nullptr, count, nullptr);
   if (!rc && hip_ok(hipDeviceSynchronize())) rc = -GPC_EDEV;
   if (!rc && hip_ok(hipMemcpy(out, dout, n * 2 * sizeof(gpc_verdict), hipMemcpyDeviceToHost))) rc = -GPC_EDEV;
   if (!rc && lb_out && hip_ok(hipMemcpy(lb_out, dlb, n * sizeof(gpc_lb_result), hipMemcpyDeviceToHost))) rc = -GPC_EDEV;
+  if (!rc && hp) rc = hp->fetch();
   if (dout) (void)hipFree(dout);
   if (dlb) (void)hipFree(dlb);
   for (void* p : allocs) (void)hipFree(p);
   return rc;
+}
+
+int gpc_classify_host_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
+                         gpc_lb_result* lb_out, int32_t count) {
+  return classify_host(ctx, slot, pk, n, out, lb_out, nullptr, count);
+}
+
+int gpc_classify_host_pin_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out,
+                             gpc_lb_result* lb_out, gpc_packet_in* recs, size_t cap, uint64_t* total, int32_t count) {
+  HostPin hp{recs, cap, total};
+  return classify_host(ctx, slot, pk, n, out, lb_out, &hp, count);
 }
 
 int gpc_counters(gpc_ctx* ctx, uint64_t** dev, const uint32_t** slot_conj, size_t* n_slots) {
@@ -2127,6 +2289,14 @@ int gpc_debug_service_image(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words
   return GPC_OK;
 }
 
+int gpc_debug_pin_image(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words) {
+  if (!ctx) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> g(ctx->ctl);
+  if (blob) *blob = ctx->pin_blob.empty() ? nullptr : ctx->pin_blob.data();
+  if (n_words) *n_words = ctx->pin_blob.size();
+  return GPC_OK;
+}
+
 int gpc_debug_service_image6(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words) {
   if (!ctx) return -GPC_EINVAL;
   std::lock_guard<std::mutex> g(ctx->ctl);
@@ -2160,7 +2330,7 @@ int gpc_launch_times(gpc_ctx* ctx, gpc_launch_time* out, size_t cap, size_t* n) 
   static const char* const names[kLaunchKinds] = {"group_tiles", "classify_egress", "classify_ingress", "classify_both",
                                                   "unpermute",   "v6_codes",        "v6_lb",            "aff_learn",
                                                   "aff_resolve", "aff_sweep",       "aff6_learn",       "aff6_resolve",
-                                                  "aff6_sweep"};
+                                                  "aff6_sweep",  "pin_count",       "pin_scan",         "pin_scatter"};
   double ms[kLaunchKinds] = {};
   uint32_t cnt[kLaunchKinds] = {};
   size_t dropped = 0;
@@ -2434,6 +2604,23 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
     ctx->svc6_blob = std::move(sb6);
     ctx->svc_gen = ctx->svc.generation();
   }
+  // the packet-in image follows the realized flows, not the image build: rebuilt only when a flow
+  // loading PacketInOperationField came, went or changed (no work per flow otherwise)
+  if (ctx->np.pin_generation() != ctx->pin_gen) {
+    ctx->pin_gen = ctx->np.pin_generation();
+    std::map<uint32_t, uint32_t> pm = ctx->np.pin_ops();
+    if (pm != ctx->pin_map) {
+      try {
+        std::vector<uint32_t> pb = build_pin_image(pm);
+        ctx->pin_blob = std::move(pb);
+      } catch (...) {
+        return -GPC_ENOMEM;
+      }
+      ctx->pin_map = std::move(pm);
+      ctx->pin_unpublished = true;
+    }
+  }
+  const bool pin_changed = ctx->pin_unpublished;
   ctx->slot_conj = ctx->slots.slot_conj();
   if (full) ctx->n_full++;
   else ctx->n_delta++;
@@ -2587,6 +2774,8 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
     if (svc_changed && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
     if (svc_changed && !ctx->svc6_blob.empty() && (rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6))) return fail(rc);
     if (svc_changed && ne[k].svc6) ne[k].svc6->affinity = svc_has_affinity(ctx->svc6_blob);
+    if (!pin_changed) ne[k].pin = D.cur.pin;
+    else if (!ctx->pin_blob.empty() && (rc = upload_words(ctx->pin_blob, D.device, us, &ne[k].pin))) return fail(rc);
     ne[k].epoch = epoch;
     // counters: grow to the slot count, zero released slots (their Metric flows were deleted)
     nc[k] = D.d_counters;
@@ -2607,6 +2796,7 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
   const clk::time_point tc3 = clk::now();
   if (tail) jn.uploaded = jn.pool.size();
   if (tail6) j6.uploaded = j6.pool.size();
+  ctx->pin_unpublished = false;
   ctx->epoch = epoch;
   std::vector<DevEpoch> old(nd);
   std::vector<unsigned long long*> old_counters(nd, nullptr);

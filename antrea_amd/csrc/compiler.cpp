@@ -734,11 +734,42 @@ void FeatureNP::note_change(const Flow& old, const Flow& nw) {
   note_flow(nw);
 }
 
+// PacketInOperationField of a conj_id flow of a rule table (0: it loads none).
+static uint32_t flow_pin_ops(const Flow& f) {
+  if (!is_rule_table(f.table) || !f.m.has_conj || !f.m.conj_id) return 0;
+  uint32_t ops = 0;
+  for (auto& a : f.acts)
+    if (a.kind == ACT_SET_REG && a.a == 0 && a.has_mask && a.c == 0xfe000000u) ops = a.b >> 25;
+  return ops;
+}
+
+void FeatureNP::note_pin(const Flow& f, bool add) {
+  const uint32_t ops = flow_pin_ops(f);
+  if (!ops) return;
+  const auto key = std::make_pair(f.m.conj_id, ops);
+  if (add) {
+    if (pin_refs_[key]++ == 0) pin_gen_++;
+  } else {
+    auto it = pin_refs_.find(key);
+    if (it != pin_refs_.end() && --it->second == 0) {
+      pin_refs_.erase(it);
+      pin_gen_++;
+    }
+  }
+}
+
+std::map<uint32_t, uint32_t> FeatureNP::pin_ops() const {
+  std::map<uint32_t, uint32_t> out;
+  for (auto& kv : pin_refs_) out[kv.first.first] = kv.first.second;  // (one value per id; the largest if flows disagree)
+  return out;
+}
+
 void FeatureNP::apply_bundle(std::vector<const Flow*> add, std::vector<const Flow*> del) {
   for (auto* f : del) {
     auto it = installed_.find(f->identity());
     if (it == installed_.end()) continue;
     note_flow(it->second);
+    note_pin(it->second, false);
     if (is_hard_flow(it->second)) hard_.erase(it->first);
     installed_.erase(it);
   }
@@ -747,12 +778,14 @@ void FeatureNP::apply_bundle(std::vector<const Flow*> add, std::vector<const Flo
     auto it = installed_.find(id);
     if (it != installed_.end()) {
       note_change(it->second, *f);
+      note_pin(it->second, false);
       if (is_hard_flow(it->second)) hard_.erase(id);
       it->second = *f;
     } else {
       note_flow(*f);
       it = installed_.emplace(std::move(id), *f).first;
     }
+    note_pin(*f, true);
     if (is_hard_flow(*f)) hard_[it->first] = *f;
   }
   generation_++;

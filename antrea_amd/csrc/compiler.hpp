@@ -148,6 +148,11 @@ class FeatureNP {
   const std::map<uint32_t, ConjPtr>& policies() const { return policy_cache_; }
   std::string dump() const;
   uint64_t generation() const { return generation_; }
+  // Packet-in bookkeeping: conj id -> PacketInOperationField (reg0[25..31]) value loaded by its
+  // realized action flows (rule-table flows that match conj_id), kept as the flow table changes;
+  // pin_generation() moves only when an id comes, goes or changes its value.
+  std::map<uint32_t, uint32_t> pin_ops() const;
+  uint64_t pin_generation() const { return pin_gen_; }
 
  private:
   // flow builders (pipeline.go)
@@ -184,6 +189,9 @@ class FeatureNP {
   uint64_t generation_ = 0;
   void note_flow(const Flow& f);
   void note_change(const Flow& old, const Flow& nw);
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> pin_refs_;  // (conj id, ops) -> realized flows loading it
+  uint64_t pin_gen_ = 0;
+  void note_pin(const Flow& f, bool add);
 };
 
 // ovs-ofctl flow text -> Flow (flowtext.cpp). 1 = parsed, 0 = skipped line (blank, header, table

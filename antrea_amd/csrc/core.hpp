@@ -3005,4 +3005,91 @@ GPC_HD void make_pkt(Pkt& p, uint32_t src, uint32_t dst, uint32_t sport, uint32_
                                   : 0u;
 }
 
+// ---------------------------------------------------------------------------- Packet-in image
+// Which conjunctions' action flows load PacketInOperationField (reg0[25..31]): conj id -> the loaded
+// value, for every realized rule-table flow that matches conj_id and loads a non-zero value there
+// (compiler.cpp FeatureNP::pin_ops). One blob for both address families (the allow flows of the two
+// IP protocols carry the same id and value). Laid out like the Service image:
+//   PinHdr at word 0; a 2^map_log2-bit presence map of the ids (pin_map_bit; ~16 bits per id, so one
+//   load settles almost every id that is not a key); a 2-choice hash of 2^hash_log2 buckets of
+//   kPinSlots {conj id, ops} slots (two 128-bit loads per bucket), compared on the whole id. Id 0 is
+//   never a key (an empty slot).
+struct PinHdr {
+  uint32_t n, map_off, map_log2, hash_off, hash_log2, pad[3];
+};
+constexpr uint32_t kPinHdrWords = 8, kPinSlots = 4, kPinBucketWords = 2 * kPinSlots;
+GPC_HD uint32_t pin_map_bit(uint32_t conj, uint32_t log2) { return mix32(conj ^ 0x3c6ef372u) >> (32u - log2); }
+GPC_HD uint32_t pin_b1(uint32_t conj, uint32_t mask) { return mix32(conj * 0x9e3779b1u + 0x7f4a7c15u) & mask; }
+GPC_HD uint32_t pin_b2(uint32_t conj, uint32_t mask) { return (mix32(conj ^ 0xa54ff53au) >> 7) & mask; }
+// PacketInOperationField of conj's action flow, 0: none (img may be null: no packet-in image).
+GPC_HD uint32_t pin_lookup(const uint32_t* img, uint32_t conj) {
+  if (!img || !conj) return 0u;
+  const PinHdr* h = reinterpret_cast<const PinHdr*>(img);
+  const uint32_t mb = pin_map_bit(conj, h->map_log2);
+  if (!((img[h->map_off + (mb >> 5)] >> (mb & 31u)) & 1u)) return 0u;
+  const uint32_t mask = (1u << h->hash_log2) - 1u;
+  const uint32_t bs[2] = {pin_b1(conj, mask), pin_b2(conj, mask)};
+  uint32_t r = 0u;
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    const uint32_t* b = img + h->hash_off + size_t(bs[c]) * kPinBucketWords;
+#pragma unroll
+    for (uint32_t i = 0; i < kPinSlots; i += 2) {
+#if defined(__HIPCC__)
+      const uint4 v = *reinterpret_cast<const uint4*>(b + 2 * i);
+      const uint32_t k0 = v.x, o0 = v.y, k1 = v.z, o1 = v.w;
+#else
+      const uint32_t k0 = b[2 * i], o0 = b[2 * i + 1], k1 = b[2 * i + 2], o1 = b[2 * i + 3];
+#endif
+      r = k0 == conj ? o0 : r;
+      r = k1 == conj ? o1 : r;
+    }
+  }
+  return r;
+}
+
+// Packet-in collection (packetin.hip): the batch is cut into tiles of kPinTile packets, one
+// workgroup each.
+constexpr uint32_t kPinTile = 1024;
+// One gpc_packet_in as its four words: {index, conj_id, category | operations << 8 | table << 16 |
+// disposition << 24, stage}.
+struct PinRec {
+  uint32_t w[4];
+};
+GPC_HD uint32_t pin_word(uint32_t category, uint32_t ops, uint32_t table, uint32_t disposition) {
+  return category | (ops << 8) | (table << 16) | (disposition << 24);
+}
+// The controller-bound records of one packet, from its verdict pair v = {egress conj, egress packed,
+// ingress conj, ingress packed} (VerdictOut) and the epoch's packet-in image: bit 0 of the result = the
+// egress stage has one (r[0]), bit 1 = the ingress stage has one (r[1]). What OVS sends the agent:
+//   - SvcReject (checked first): the packet was rejected in EndpointDNAT (a Service without
+//     Endpoints); one record of category 4, stage 0, disposition 2, and no other;
+//   - per stage, DNS: the deciding flow has the controller action (GPC_VFLAG_PACKETIN); category 2;
+//   - per stage, NP: ALLOW / DROP / REJECT by a conjunction whose action flow loads
+//     PacketInOperationField (logging, deny tracking, reject); category 1, the field's value verbatim.
+// NONE, NO_MATCH, BYPASS without the flag and ISOLATION_DROP give nothing.
+GPC_HD uint32_t pin_records(uint32_t index, const uint32_t v[4], const uint32_t* img, PinRec r[2]) {
+  if ((v[1] & 0xffffu) == (uint32_t(GPC_ACT_REJECT) | uint32_t(GPC_VTABLE_ENDPOINT_DNAT) << 8)) {
+    r[0] = PinRec{{index, 0u, pin_word(GPC_PIN_CAT_SVC_REJECT, 0u, 0u, 2u), 0u}};
+    return 1u;
+  }
+  uint32_t m = 0u;
+#pragma unroll
+  for (uint32_t s = 0; s < 2; s++) {
+    const uint32_t conj = v[2 * s], p = v[2 * s + 1];
+    const uint32_t act = p & 0xffu, table = 3u * s + ((p >> 8) & 0xffu);
+    if ((p >> 24) & GPC_VFLAG_PACKETIN) {
+      r[s] = PinRec{{index, conj, pin_word(GPC_PIN_CAT_DNS, 0u, table, 0u), s}};
+      m |= 1u << s;
+    } else if (act >= GPC_ACT_ALLOW && act <= GPC_ACT_REJECT) {
+      const uint32_t ops = pin_lookup(img, conj);
+      if (ops) {
+        r[s] = PinRec{{index, conj, pin_word(GPC_PIN_CAT_NP, ops, table, act - GPC_ACT_ALLOW), s}};
+        m |= 1u << s;
+      }
+    }
+  }
+  return m;
+}
+
 }  // namespace gpc

@@ -47,14 +47,15 @@ uint64_t group_scratch_bytes(const gpc_pkt_soa& pk, uint64_t n, bool lb);
 // Launch timing (gpc_set_launch_timing): an event is recorded on the launch stream before every
 // kernel of one gpc_classify* call and after the last, named by the kernel that follows it.
 struct LaunchMarks {
-  static constexpr int kMax = 12;
+  static constexpr int kMax = 16;
   hipEvent_t ev[kMax];
   uint8_t kind[kMax];  // LaunchKind of the kernel starting at ev[i] (kLaunchEnd: the closing event)
   int n;
 };
 enum LaunchKind : uint8_t {
   kLaunchGroup, kLaunchEgress, kLaunchIngress, kLaunchBoth, kLaunchUnpermute, kLaunchCodes, kLaunchV6Lb, kLaunchAffLearn, kLaunchAffResolve,
-  kLaunchAffSweep, kLaunchAff6Learn, kLaunchAff6Resolve, kLaunchAff6Sweep, kLaunchKinds, kLaunchEnd
+  kLaunchAffSweep, kLaunchAff6Learn, kLaunchAff6Resolve, kLaunchAff6Sweep, kLaunchPinCount, kLaunchPinScan, kLaunchPinScatter,
+  kLaunchKinds, kLaunchEnd
 };
 inline void launch_mark(LaunchMarks* m, uint8_t kind, hipStream_t s) {
   if (!m || m->n >= LaunchMarks::kMax) return;
@@ -126,4 +127,14 @@ int launch_aff_sweep(const AffTable& t, uint32_t now, uint32_t mode, hipStream_t
 int launch_classify_aff(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out, uint4* lb_out,
                         unsigned long long* counters, int count, const GroupArgs* group, hipStream_t stream,
                         LaunchMarks* marks, const AffLaunch& al, gpc_pkt_soa* rewritten = nullptr);
+// Packet-in collection (packetin.hip): an ordered stream compaction of the batch's controller-bound
+// records (core.hpp pin_records over the verdict pairs `out` and the epoch's packet-in image `img`,
+// null: none) in three launches on `stream` -- pin_count_kernel (per wave the two lane masks, per
+// tile of kPinTile packets the record count), pin_scan_kernel (one workgroup: exclusive 64-bit scan
+// of the tile counts, the total to *count), pin_scatter_kernel (records[position] for positions
+// < cap). No workgroup waits for another and nothing is atomic: the order is the packet order.
+// scratch: pin_scratch_bytes(n) bytes, 16-byte aligned. n > 0.
+uint64_t pin_scratch_bytes(uint64_t n);
+int launch_pin(const uint32_t* img, const gpc_verdict* out, uint64_t n, gpc_packet_in* records, uint64_t cap,
+               unsigned long long* count, void* scratch, hipStream_t stream, LaunchMarks* marks);
 }

@@ -49,6 +49,12 @@ AFF_ENTRY6_DTYPE = np.dtype([("install_id", "<u4"), ("endpoint_port", "<u4"), ("
                              ("src", "u1", (16,)), ("dst", "u1", (16,)), ("endpoint_ip", "u1", (16,))])
 VFLAG_PASS, VFLAG_TIE, VFLAG_PACKETIN = 1, 2, 4  # gpc_verdict.flags
 VTABLE_ENDPOINT_DNAT = 4
+# gpc_packet_in (16 B): one controller-bound record of the packet-in queue
+PACKET_IN_DTYPE = np.dtype([("index", "<u4"), ("conj_id", "<u4"), ("category", "u1"), ("operations", "u1"), ("table", "u1"),
+                            ("disposition", "u1"), ("stage", "u1"), ("reserved", "u1", (3,))])
+PIN_CAT_NP, PIN_CAT_DNS, PIN_CAT_SVC_REJECT = 1, 2, 4       # gpc_packet_in.category
+PIN_OP_LOGGING, PIN_OP_STORE_DENY, PIN_OP_REJECT = 1, 2, 4  # gpc_packet_in.operations
+PIN_TILE = 1024  # core.hpp kPinTile: packets per workgroup of the collection passes
 
 
 class gpc_config(C.Structure):
@@ -86,6 +92,11 @@ class gpc_pkt_soa(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("src", "dst", "sport", "dport", "proto", "out_port", "in_port", "svc_group",
                                           "tun_id", "ct_src", "ct_dst", "ct_state", "dest", "len",
                                           "src6", "dst6", "ct_src6", "ct_dst6", "ct_mark")]
+
+
+class gpc_pin_queue(C.Structure):
+    _fields_ = [("records", C.c_void_p), ("cap", C.c_uint64), ("count", C.c_void_p), ("scratch", C.c_void_p),
+                ("scratch_bytes", C.c_size_t)]
 
 
 class gpc_trace_step(C.Structure):
@@ -158,7 +169,8 @@ EXPORTS = ["gpc_create", "gpc_destroy", "gpc_initialize", "gpc_install_rule", "g
            "gpc_set_affinity_clock", "gpc_affinity_stats", "gpc_debug_affinity_table", "gpc_debug_set_affinity_seq",
            "gpc_affinity_stats6", "gpc_debug_affinity_table6", "gpc_debug_set_affinity_seq6",
            "gpc_debug_set_affinity6_digest_bits", "gpc_debug_counter_layout", "gpc_trace_on", "gpc_trace6",
-           "gpc_debug_v6_prefix_of_code"]
+           "gpc_debug_v6_prefix_of_code", "gpc_pin_scratch_bytes", "gpc_classify_pin_on", "gpc_classify6_pin_on",
+           "gpc_classify_host_pin_on", "gpc_classify6_host_pin", "gpc_debug_pin_image"]
 
 _lib = None
 
@@ -247,6 +259,12 @@ def load(path: str = LIB_PATH):
     lib.gpc_debug_affinity_table6.argtypes = [vp, C.c_uint32, vp, sz, C.POINTER(sz)]
     lib.gpc_debug_set_affinity_seq6.argtypes = [vp, C.c_uint32, C.c_uint32]
     lib.gpc_debug_set_affinity6_digest_bits.argtypes = [vp, C.c_uint32, C.c_uint32]
+    lib.gpc_pin_scratch_bytes.argtypes = [sz, C.POINTER(sz)]
+    lib.gpc_classify_pin_on.argtypes = [vp, C.c_uint32, C.POINTER(gpc_pkt_soa), sz, vp, vp, C.POINTER(gpc_pin_queue), i32, vp]
+    lib.gpc_classify6_pin_on.argtypes = [vp, C.c_uint32, C.POINTER(gpc_pkt_soa), sz, vp, vp, C.POINTER(gpc_pin_queue), i32, vp]
+    lib.gpc_classify_host_pin_on.argtypes = [vp, C.c_uint32, C.POINTER(gpc_pkt_soa), sz, vp, vp, vp, sz, C.POINTER(C.c_uint64), i32]
+    lib.gpc_classify6_host_pin.argtypes = [vp, C.POINTER(gpc_pkt_soa), sz, vp, vp, vp, sz, C.POINTER(C.c_uint64), i32]
+    lib.gpc_debug_pin_image.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(sz)]
     lib.gpc_strerror.argtypes = [i32]
     lib.gpc_strerror.restype = C.c_char_p
     _lib = lib
@@ -745,6 +763,59 @@ class Classifier:
                                               int(count)), "gpc_classify6_host")
         return (out.reshape(n, 2), lbo) if lb else out.reshape(n, 2)
 
+    def classify_host_pin(self, cols: Dict[str, np.ndarray], cap: int, count=False, lb=False, slot=0):
+        """classify_host plus the batch's packet-in queue: (verdicts (n, 2), records (min(total, cap),) of
+        PACKET_IN_DTYPE, total) -- with lb=True the Service stage results follow the verdicts."""
+        soa, keep, n = pkt_soa_host(cols)
+        out = np.zeros(2 * n, dtype=VERDICT_DTYPE)
+        lbo = np.zeros(n, dtype=LB_DTYPE) if lb else None
+        recs = np.zeros(int(cap), dtype=PACKET_IN_DTYPE)
+        total = C.c_uint64()
+        _check(self.lib.gpc_classify_host_pin_on(self.h, int(slot), C.byref(soa), n, out.ctypes.data,
+                                                 lbo.ctypes.data if lb else None, recs.ctypes.data if cap else None, int(cap),
+                                                 C.byref(total), int(count)), "gpc_classify_host_pin_on")
+        recs = recs[:min(total.value, int(cap))]
+        return (out.reshape(n, 2), lbo, recs, total.value) if lb else (out.reshape(n, 2), recs, total.value)
+
+    def classify6_host_pin(self, cols: Dict[str, np.ndarray], cap: int, count=False, lb=False):
+        """classify6_host plus the batch's packet-in queue (as classify_host_pin; LB6_DTYPE results)."""
+        soa, keep, n = pkt_soa_host(cols)
+        out = np.zeros(2 * n, dtype=VERDICT_DTYPE)
+        lbo = np.zeros(n, dtype=LB6_DTYPE) if lb else None
+        recs = np.zeros(int(cap), dtype=PACKET_IN_DTYPE)
+        total = C.c_uint64()
+        _check(self.lib.gpc_classify6_host_pin(self.h, C.byref(soa), n, out.ctypes.data, lbo.ctypes.data if lb else None,
+                                               recs.ctypes.data if cap else None, int(cap), C.byref(total), int(count)),
+               "gpc_classify6_host_pin")
+        recs = recs[:min(total.value, int(cap))]
+        return (out.reshape(n, 2), lbo, recs, total.value) if lb else (out.reshape(n, 2), recs, total.value)
+
+    @staticmethod
+    def pin_scratch_bytes(n: int) -> int:
+        b = C.c_size_t()
+        _check(load().gpc_pin_scratch_bytes(int(n), C.byref(b)), "gpc_pin_scratch_bytes")
+        return b.value
+
+    def classify_pin_device(self, soa: gpc_pkt_soa, n: int, out_ptr: int, queue: gpc_pin_queue, count=False, stream: int = 0,
+                            lb_ptr: int = 0, slot=0):
+        """gpc_classify_pin_on: device columns; `queue` names device memory (records, count, scratch of
+        pin_scratch_bytes(n) bytes). The queue is complete when the stream has passed the call."""
+        _check(self.lib.gpc_classify_pin_on(self.h, int(slot), C.byref(soa), n, out_ptr, lb_ptr or None, C.byref(queue),
+                                            int(count), stream or None), "gpc_classify_pin_on")
+
+    def classify6_pin_device(self, soa: gpc_pkt_soa, n: int, out_ptr: int, queue: gpc_pin_queue, count=False,
+                             stream: int = 0, lb_ptr: int = 0, slot=0):
+        """gpc_classify6_pin_on (lb_ptr: n gpc_lb_result6, 16-B aligned)."""
+        _check(self.lib.gpc_classify6_pin_on(self.h, int(slot), C.byref(soa), n, out_ptr, lb_ptr or None, C.byref(queue),
+                                             int(count), stream or None), "gpc_classify6_pin_on")
+
+    def debug_pin_image(self):
+        """(blob pointer, n_words) of the committed packet-in image ((None, 0) when absent)."""
+        b = C.POINTER(C.c_uint32)()
+        n = C.c_size_t()
+        _check(self.lib.gpc_debug_pin_image(self.h, C.byref(b), C.byref(n)), "gpc_debug_pin_image")
+        return (C.cast(b, C.c_void_p).value if n.value else None), n.value
+
     def classify6_device(self, soa: gpc_pkt_soa, n: int, out_ptr: int, count=False, stream: int = 0, slot=0):
         _check(self.lib.gpc_classify6_on(self.h, int(slot), C.byref(soa), n, out_ptr, int(count), stream or None),
                "gpc_classify6")
@@ -824,9 +895,9 @@ class Classifier:
 
     def launch_times(self) -> Dict[str, dict]:
         """gpc_launch_times: {kernel: {"launches", "total_ms", "mean_ms", "dropped"}} since the last call."""
-        arr = (gpc_launch_time * 16)()
+        arr = (gpc_launch_time * 24)()
         n = C.c_size_t()
-        _check(self.lib.gpc_launch_times(self.h, arr, 16, C.byref(n)), "gpc_launch_times")
+        _check(self.lib.gpc_launch_times(self.h, arr, 24, C.byref(n)), "gpc_launch_times")
         return {arr[i].kernel.decode(): {"launches": arr[i].launches, "total_ms": arr[i].total_ms,
                                          "mean_ms": arr[i].total_ms / max(1, arr[i].launches),
                                          "dropped": arr[i].dropped} for i in range(n.value)}

@@ -672,6 +672,74 @@ int gpc_reset_counters(gpc_ctx* ctx);
  * larger array and merges the old one into it. -GPC_EINVAL for a slot out of range. */
 int gpc_debug_counter_layout(gpc_ctx* ctx, uint32_t slot, size_t* cap, uint32_t* copies);
 
+/* ------------------------------------------------------------------------------ packet-in queue */
+/* The packets of a batch that OVS would send to the agent's packet-in handlers (packetin.go), as an
+ * ordered list the device builds behind the classification: one record per packet and stage whose
+ * deciding flow sends the packet to the controller -- audit logging (gpc_rule.enable_logging),
+ * Reject (the agent synthesises the RST / ICMP reply), deny tracking
+ * (gpc_config.enable_deny_tracking), the DNS conjunction (FQDN), and a Service without Endpoints
+ * (SvcReject). Ascending packet index; a packet's egress record before its ingress record.
+ *
+ * Per stage s (0 egress, 1 ingress) of a packet with verdicts v[2]:
+ *   - SvcReject, checked first: v[0] is REJECT at GPC_VTABLE_ENDPOINT_DNAT -> one record {category
+ *     SVC_REJECT, stage 0, disposition 2, everything else 0}; the packet gets no other record;
+ *   - DNS: v[s].flags & GPC_VFLAG_PACKETIN -> {category DNS, conj_id, table, operations 0, disposition 0};
+ *   - NP: v[s].action is ALLOW / DROP / REJECT and the action flow of v[s].conj_id loads a non-zero
+ *     PacketInOperationField (reg0[25..31]) -> {category NP, conj_id, that value as `operations`,
+ *     table, disposition 0 / 1 / 2}.
+ * `table` is the gpc_table (1..6) the deciding flow loads into PacketInTableField.
+ *
+ * Deliberately not reported (the walk would have to hand out the deciding flow; installing such rules
+ * behaves as before): a Pass rule with enable_logging (the verdict keeps GPC_VFLAG_PASS, not the
+ * passing rule's id), and the K8s default-drop flows with logging or deny tracking (ISOLATION_DROP
+ * verdicts carry no flow id). gpc_trace* is unchanged. */
+#define GPC_PIN_CAT_NP 1         /* PacketInCategoryNP (packetin.go:45-55)   */
+#define GPC_PIN_CAT_DNS 2        /* PacketInCategoryDNS                      */
+#define GPC_PIN_CAT_SVC_REJECT 4 /* PacketInCategorySvcReject                */
+/* PacketInOperationField bits as this library's compiler assigns them (the value is reported verbatim) */
+#define GPC_PIN_OP_LOGGING 1
+#define GPC_PIN_OP_STORE_DENY 2
+#define GPC_PIN_OP_REJECT 4
+typedef struct gpc_packet_in {   /* 16 bytes */
+  uint32_t index;                /* packet index in the batch */
+  uint32_t conj_id;              /* deciding conjunction (0: SvcReject) */
+  uint8_t category;              /* GPC_PIN_CAT_* */
+  uint8_t operations;            /* PacketInOperationField of the deciding flow, GPC_PIN_OP_* (NP only, else 0) */
+  uint8_t table;                 /* gpc_table 1..6 = PacketInTableField; 0: SvcReject */
+  uint8_t disposition;           /* APDispositionField: 0 allow, 1 drop, 2 reject */
+  uint8_t stage;                 /* 0 egress, 1 ingress */
+  uint8_t reserved[3];           /* 0 */
+} gpc_packet_in;
+typedef struct gpc_pin_queue {
+  gpc_packet_in* records;        /* device, cap entries, 16-byte aligned; may be NULL when cap == 0 */
+  uint64_t cap;
+  uint64_t* count;               /* device: records the batch produced; the first min(count, cap) are stored */
+  void* scratch;                 /* device, >= gpc_pin_scratch_bytes(n), 16-byte aligned */
+  size_t scratch_bytes;
+} gpc_pin_queue;
+/* Scratch a batch of n packets needs (two 64-bit lane masks per 64 packets, one 64-bit count per tile).
+ * n > GPC_MAX_BATCH: -GPC_EINVAL. */
+int gpc_pin_scratch_bytes(size_t n, size_t* bytes);
+/* gpc_classify_on / gpc_classify6_lb_on plus the packet-in queue of the batch: the same launches,
+ * then three more on the same stream (pin_count, pin_scan, pin_scatter), bound to the same epoch as
+ * the verdicts. Verdicts, lb_out and counters are those of the call without a queue. Nothing is
+ * written behind min(*count, cap) records. n == 0: *count = 0 (stream-ordered), nothing launched.
+ * -GPC_EINVAL, nothing launched: q or q->count NULL, records NULL with cap > 0, scratch NULL or too
+ * small with n > 0, records / scratch not 16-byte aligned, count not 8-byte aligned. */
+int gpc_classify_pin_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out,
+                        gpc_lb_result* lb_out, const gpc_pin_queue* q, int32_t count, void* stream);
+int gpc_classify6_pin_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out,
+                         gpc_lb_result6* lb_out, const gpc_pin_queue* q, int32_t count, void* stream);
+/* The same with HOST pointers (copies in and out; synchronous): recs receives the first
+ * min(*total, cap) records (may be NULL when cap == 0), *total the number the batch produced. */
+int gpc_classify_host_pin_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out,
+                             gpc_lb_result* lb_out, gpc_packet_in* recs, size_t cap, uint64_t* total, int32_t count);
+int gpc_classify6_host_pin(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
+                           gpc_packet_in* recs, size_t cap, uint64_t* total, int32_t count);
+/* The host copy of the committed packet-in image (core.hpp PinHdr; NULL / 0 when no realized flow
+ * loads PacketInOperationField). It is rebuilt only by a commit after such a flow came or went. */
+int gpc_debug_pin_image(gpc_ctx* ctx, const uint32_t** blob, size_t* n_words);
+
 /* ---------------------------------------------------------------------------- introspection */
 /* ovs-ofctl style dump of the realized flow table (utils.go FlowModToString), '\n' separated. */
 int gpc_dump_flows(gpc_ctx* ctx, char* buf, size_t cap, size_t* needed);
@@ -707,7 +775,8 @@ int gpc_stream_epoch(gpc_ctx* ctx, void* stream, uint64_t* epoch);
  * slots = 0 (the default) records nothing. */
 typedef struct gpc_launch_time {
   char kernel[32];   /* "group_tiles", "classify_egress", "classify_ingress", "classify_both", "unpermute",
-                        "v6_codes", "v6_lb", "aff_learn", "aff_resolve", "aff_sweep" */
+                        "v6_codes", "v6_lb", "aff_learn", "aff_resolve", "aff_sweep"; calls with a packet-in
+                        queue only: "pin_count", "pin_scan", "pin_scatter" */
   uint32_t launches; /* launches of that kernel since the previous gpc_launch_times */
   uint32_t dropped;  /* event sets overwritten before they were read (all kinds) */
   double total_ms;   /* summed HIP-event durations */

@@ -100,6 +100,9 @@ struct DevImage {  // one uploaded image (freed when the last epoch using it ret
   uint32_t axes = 0;                    // axes read by the sub-indexes (group_axes)
   bool composite = false;               // some table has a composite driver index (TableHdr n_cidx)
   bool affinity = false;                // a Service image with session-affinity Services (SvcHdr n_aff)
+  // an IPv6 base: the prefix tree its codes come from (gpc_trace6 translates a slot's codes through
+  // the tree of the base that slot publishes; the host image may be a newer build whose upload failed)
+  std::shared_ptr<V6Codes> codes6;
   ~DevImage() {
     int cur = 0;
     const bool swap = hipGetDevice(&cur) == hipSuccess && cur != device;
@@ -240,6 +243,12 @@ struct gpc_ctx {
   // waiting commit (std::mutex is not fair): measured 0.8-1.5 s per commit beside classification.
   std::atomic<uint32_t> publishers{0};
   std::atomic<int> fail_uploads{0};  // gpc_debug_fail_uploads: this context's next commit / replay uploads fail
+  // gpc_debug_fail_upload_at / gpc_debug_upload_points (dev_point): the armed skip count (-1: none),
+  // the countdown of the commit / compact / replay in progress, the points it has passed and the
+  // points the last one passed. The last three under `ctl`.
+  std::atomic<int> fail_at{-1};
+  int fail_left = -1;
+  uint32_t points_cur = 0, points_last = 0;
   // Launch pacing (pace_take): per (slot, stream), the events after the last kPaceDepth calls.
   std::mutex pace_mu;
   std::map<std::pair<uint32_t, StreamKey>, std::deque<hipEvent_t>> pace;
@@ -254,6 +263,11 @@ struct gpc_ctx {
   std::map<uint32_t, uint32_t> pin_map;
   uint64_t pin_gen = 0;
   bool pin_unpublished = false;          // pin_blob changed and no commit has put it on the device slots yet
+  // the same for svc_blob / svc6_blob (a failed commit has already taken svc_gen), and for a journal
+  // that a pool collection rewrote from word 0: the device pools still hold the old layout, so the
+  // next epoch takes fresh ones
+  bool svc_unpublished = false;
+  bool pool_unpublished = false;
   SlotMap slots;
   HostImage last;    // base image of the current epoch: shadow state for re-upload + debug export
   HostImage last6;   // IPv6 base image (ipv6_enabled)
@@ -284,7 +298,8 @@ struct gpc_ctx {
   void* stage = nullptr;                 // pinned staging buffer of journal uploads
   size_t stage_bytes = 0;
   std::vector<uint32_t> released_slots;
-  std::vector<uint32_t> slot_conj;
+  std::vector<uint32_t> slot_conj;       // of the published epoch (gpc_counters, gpc_metrics)
+  std::vector<uint32_t> slot_conj_next;  // of the host images: becomes slot_conj when they are published
   uint64_t epoch = 0, n_full = 0, n_delta = 0, n_bg = 0, n_pool_gc = 0;
   uint64_t commit_no = 0;                // commits so far (COMMIT markers in the log)
   bool comp_pending = false;             // a background compaction was requested, not installed yet
@@ -330,6 +345,15 @@ static void log_op(gpc_ctx* ctx, Op&& op) {
 }
 
 static int hip_ok(hipError_t e) { return e == hipSuccess ? 0 : -GPC_EDEV; }
+
+// The conj id of every counter slot, for gpc_counters / gpc_metrics / gpc_image_stats (`ctl` held):
+// of the published epoch -- the device counts for that one, whatever a failed commit has staged
+// since. While no slot publishes anything (before the first publish, after a gpc_replay that
+// failed; every count is zero then) it is the map of the host images, which a host without a
+// device reads after a commit that could only build them.
+static const std::vector<uint32_t>& slot_map(const gpc_ctx* ctx) {
+  return ctx->cur_epoch ? ctx->slot_conj : ctx->slot_conj_next;
+}
 
 // Per-rule counters are device-scope 64-bit atomics; with few rules (C1: 30 slots) every packet's
 // update lands on a handful of addresses and serializes (64 M packets: 137 ms with counters vs
@@ -489,11 +513,36 @@ struct Pace {
   }
 };
 
-// fail: the context's gpc_debug_fail_uploads counter (commit / replay uploads only; the background
-// compactor's uploads pass none)
+// Failure injection (gpc_debug_fail_upload_at): every device allocation, copy and synchronize of a
+// commit, compact or replay passes here first, in program order, under `ctl`. True: the caller
+// returns -GPC_EDEV instead of making the call. A null context (the background compactor) never fails.
+static bool dev_point(gpc_ctx* ctx) {
+  if (!ctx) return false;
+  ctx->points_cur++;
+  if (ctx->fail_left < 0) return false;
+  return ctx->fail_left-- == 0;
+}
+
+// Brackets one commit / compact / replay (`ctl` held): takes the armed skip count, so the hook fires
+// at most once and only in this call, and records the points passed when the call returns.
+struct PointScope {
+  gpc_ctx* ctx;
+  explicit PointScope(gpc_ctx* c) : ctx(c) {
+    ctx->points_cur = 0;
+    ctx->fail_left = ctx->fail_at.exchange(-1);
+  }
+  ~PointScope() {
+    ctx->points_last = ctx->points_cur;
+    ctx->fail_left = -1;
+  }
+};
+
+// ctx: the context whose commit / replay uploads (dev_point, and its gpc_debug_fail_uploads counter);
+// the background compactor's uploads pass none
 static int upload_image(const HostImage& h, int device, hipStream_t s, std::shared_ptr<DevImage>* out,
-                        std::atomic<int>* fail = nullptr) {
-  if (fail && fail->load() > 0 && fail->fetch_sub(1) > 0) return -GPC_EDEV;
+                        gpc_ctx* ctx = nullptr) {
+  if (dev_point(ctx)) return -GPC_EDEV;
+  if (ctx && ctx->fail_uploads.load() > 0 && ctx->fail_uploads.fetch_sub(1) > 0) return -GPC_EDEV;
   auto d = std::make_shared<DevImage>();
   d->s = s;
   d->device = device;
@@ -504,12 +553,15 @@ static int upload_image(const HostImage& h, int device, hipStream_t s, std::shar
     return -GPC_EDEV;
   lane_sort_tables(h, d->sort_table);
   d->axes = group_axes(h);
+  d->codes6 = h.codes6;
   for (const TableHdr& th : h.hdr.t) d->composite = d->composite || th.n_cidx != 0;
   *out = std::move(d);
   return GPC_OK;
 }
 
-static int upload_words(const std::vector<uint32_t>& w, int device, hipStream_t s, std::shared_ptr<DevImage>* out) {
+static int upload_words(const std::vector<uint32_t>& w, int device, hipStream_t s, std::shared_ptr<DevImage>* out,
+                        gpc_ctx* ctx) {
+  if (dev_point(ctx)) return -GPC_EDEV;
   auto d = std::make_shared<DevImage>();
   d->s = s;
   d->device = device;
@@ -576,7 +628,8 @@ static void collect_retired(DevState& D, bool wait) {  // the slot's device is c
 }
 
 // A new journal pool on one slot (kPoolWords words, stream-ordered allocation).
-static int alloc_pool(int device, hipStream_t s, std::shared_ptr<DevImage>* out) {
+static int alloc_pool(int device, hipStream_t s, std::shared_ptr<DevImage>* out, gpc_ctx* ctx = nullptr) {
+  if (dev_point(ctx)) return -GPC_EDEV;
   auto pool = std::make_shared<DevImage>();
   pool->s = s;
   pool->device = device;
@@ -1123,9 +1176,23 @@ int gpc_debug_fail_uploads(gpc_ctx* ctx, int n) {
   return GPC_OK;
 }
 
+int gpc_debug_fail_upload_at(gpc_ctx* ctx, int skip) {
+  if (!ctx) return -GPC_EINVAL;
+  ctx->fail_at.store(skip >= 0 ? skip : -1);
+  return GPC_OK;
+}
+
+int gpc_debug_upload_points(gpc_ctx* ctx, uint32_t* n) {
+  if (!ctx || !n) return -GPC_EINVAL;
+  std::lock_guard<std::mutex> g(ctx->ctl);
+  *n = ctx->points_last;
+  return GPC_OK;
+}
+
 int gpc_replay(gpc_ctx* ctx) {
   if (!ctx) return -GPC_EINVAL;
   std::lock_guard<std::mutex> g(ctx->ctl);
+  PointScope points(ctx);
   {  // a background compaction result built on the old device state is dropped
     std::lock_guard<std::mutex> c(ctx->comp.mu);
     if (ctx->comp.busy) ctx->comp.discard = true;
@@ -1143,6 +1210,8 @@ int gpc_replay(gpc_ctx* ctx) {
       D.cur = DevEpoch();
       old[k].d_counters = D.d_counters;
       D.d_counters = nullptr;
+      D.counter_cap = 0;  // (with the array: a commit that finds the slot empty allocates it again)
+      D.counter_copies = 1;
       D.launch_epoch.clear();
       old[k].scratch.swap(D.scratch);
       old[k].retired.swap(D.retired);
@@ -1165,6 +1234,9 @@ int gpc_replay(gpc_ctx* ctx) {
     drop_slot(O);
     (void)hipGetLastError();
   }
+  // No slot holds a Service, packet-in or journal image now: if the uploads below fail, the next
+  // commit sends them all again, as it does the bases (no base on the slot) and the counters.
+  ctx->svc_unpublished = ctx->pin_unpublished = true;
   if (drop_rc) return drop_rc;
   if (ctx->last.blob.empty()) return GPC_OK;  // nothing committed yet
   const size_t cap = std::max<size_t>(1, ctx->slots.size());
@@ -1183,35 +1255,36 @@ int gpc_replay(gpc_ctx* ctx) {
     hipStream_t us = D.ustream;
     ne[k].base_gen = ctx->gen4;
     ne[k].v6_gen = ctx->gen6;
-    rc = upload_image(ctx->last, D.device, us, &ne[k].base, &ctx->fail_uploads);
+    rc = upload_image(ctx->last, D.device, us, &ne[k].base, ctx);
     if (!rc && jn.active()) {
-      rc = alloc_pool(D.device, us, &ne[k].pool);
-      if (!rc && hip_ok(hipMemcpyAsync(ne[k].pool->d_blob, jn.pool.data(), jn.pool.size() * 4, hipMemcpyHostToDevice, us)))
+      rc = alloc_pool(D.device, us, &ne[k].pool, ctx);
+      if (!rc && (dev_point(ctx) ||
+                  hip_ok(hipMemcpyAsync(ne[k].pool->d_blob, jn.pool.data(), jn.pool.size() * 4, hipMemcpyHostToDevice, us))))
         rc = -GPC_EDEV;
       ne[k].jhdr = jn.hdr_off;
       ne[k].jmode = jn.mode();
     }
     if (!rc && !ctx->last6.blob.empty()) {
-      rc = upload_image(ctx->last6, D.device, us, &ne[k].v6, &ctx->fail_uploads);
+      rc = upload_image(ctx->last6, D.device, us, &ne[k].v6, ctx);
       ne[k].v6_lpm = ctx->last6.hdr.v6_lpm;
       const Journal& j6 = ctx->journal6;
       if (!rc && j6.active()) {
-        rc = alloc_pool(D.device, us, &ne[k].v6_pool);
-        if (!rc && hip_ok(hipMemcpyAsync(ne[k].v6_pool->d_blob, j6.pool.data(), j6.pool.size() * 4,
-                                         hipMemcpyHostToDevice, us)))
+        rc = alloc_pool(D.device, us, &ne[k].v6_pool, ctx);
+        if (!rc && (dev_point(ctx) || hip_ok(hipMemcpyAsync(ne[k].v6_pool->d_blob, j6.pool.data(), j6.pool.size() * 4,
+                                                            hipMemcpyHostToDevice, us))))
           rc = -GPC_EDEV;
         ne[k].v6_jhdr = j6.hdr_off;
       }
     }
-    if (!rc && !ctx->svc_blob.empty()) rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc);
+    if (!rc && !ctx->svc_blob.empty()) rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc, ctx);
     if (!rc && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
-    if (!rc && !ctx->svc6_blob.empty()) rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6);
+    if (!rc && !ctx->svc6_blob.empty()) rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6, ctx);
     if (!rc && ne[k].svc6) ne[k].svc6->affinity = svc_has_affinity(ctx->svc6_blob);
-    if (!rc && !ctx->pin_blob.empty()) rc = upload_words(ctx->pin_blob, D.device, us, &ne[k].pin);
-    if (!rc && (hip_ok(hipMalloc(&nc[k], cap * kCounterBytes * (copies + 1))) ||
+    if (!rc && !ctx->pin_blob.empty()) rc = upload_words(ctx->pin_blob, D.device, us, &ne[k].pin, ctx);
+    if (!rc && (dev_point(ctx) || hip_ok(hipMalloc(&nc[k], cap * kCounterBytes * (copies + 1))) || dev_point(ctx) ||
                 hip_ok(hipMemset(nc[k], 0, cap * kCounterBytes * (copies + 1)))))
       rc = -GPC_EDEV;
-    if (!rc) rc = hip_ok(hipStreamSynchronize(us));
+    if (!rc) rc = dev_point(ctx) ? -GPC_EDEV : hip_ok(hipStreamSynchronize(us));
   }
   if (rc) {
     for (size_t k = 0; k < ctx->dev.size(); k++) {
@@ -1223,7 +1296,8 @@ int gpc_replay(gpc_ctx* ctx) {
   }
   if (jn.active()) jn.uploaded = jn.pool.size();
   if (ctx->journal6.active()) ctx->journal6.uploaded = ctx->journal6.pool.size();
-  ctx->pin_unpublished = false;
+  ctx->pin_unpublished = ctx->svc_unpublished = ctx->pool_unpublished = false;
+  ctx->slot_conj = ctx->slot_conj_next;  // (the host images of a commit that failed are published here too)
   const uint64_t epoch = ++ctx->epoch;
   PublishLock d(ctx->data, ctx->publishers);
   for (size_t k = 0; k < ctx->dev.size(); k++) {
@@ -1797,9 +1871,10 @@ int gpc_trace_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict
 }
 
 // Lock order: ctx->ctl, then ctx->data -- the order gpc_commit takes them in. `ctl` is held for the
-// whole call: the codes are translated through the prefix tree of the IPv6 host image
-// (last6.codes6), which a delta commit extends in place (V6Codes::add_leaf) and a full one replaces,
-// both under `ctl`; holding it from before the launch keeps the tree the one of the traced epoch.
+// whole call: the codes are translated through the prefix tree of the traced slot's IPv6 base
+// (DevImage::codes6: the host image's tree as of that upload), which a delta commit extends in place
+// (V6Codes::add_leaf, no code changes) under `ctl`; a full build makes a new tree, which becomes the
+// slot's only when its base is published there -- not when that commit fails.
 // `data` is held for the launch alone (the epoch stays alive while it is current).
 int gpc_trace6(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict* out, gpc_lb_result6* lb_out,
                gpc_trace6_addr* addrs, gpc_trace_step* steps, size_t cap, size_t* n_steps) {
@@ -1840,10 +1915,12 @@ int gpc_trace6(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict* 
   for (size_t c = 0; c < ncol; c++)
     if (cols[c].h) *cols[c].d = buf + kOut + c * kSlot;
   int rc = hip_ok(hipMemcpy(buf, h.data(), h.size(), hipMemcpyHostToDevice));
+  HostImage traced;  // (only its prefix tree is set)
   if (!rc) {
     std::lock_guard<std::mutex> dl(ctx->data);
     DevState& D = ctx->dev[slot];
     const DevEpoch& cur = D.cur;
+    traced.codes6 = cur.v6->codes6;
     EpochArgs ep{cur.v6->d_hdr, cur.v6->d_blob, cur.v6_jhdr ? cur.v6_pool->d_blob : nullptr, cur.v6_jhdr,
                  nullptr, cur.v6_lpm, {0, 0}, 0u, 0u};
     Trace6Args t{};
@@ -1880,7 +1957,7 @@ int gpc_trace6(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict* 
       if (!(codes[4 + k] & GPC_T6_PRESENT)) continue;
       a.code = codes[k];
       a.flags = codes[4 + k];
-      if (v6_prefix_of_code(ctx->last6, codes[k], a.prefix, &a.prefix_len)) rc = -GPC_EINVAL;
+      if (v6_prefix_of_code(traced, codes[k], a.prefix, &a.prefix_len)) rc = -GPC_EINVAL;
     }
   }
   if (rc) return rc;
@@ -2166,8 +2243,8 @@ int gpc_counters_on(gpc_ctx* ctx, uint32_t slot, uint64_t** dev, const uint32_t*
   DevState& D = ctx->dev[slot];
   if (int rc = fold_counters(D)) return rc;  // the caller sees one array (the published one)
   if (dev) *dev = reinterpret_cast<uint64_t*>(published_counters(D));
-  if (slot_conj) *slot_conj = ctx->slot_conj.data();
-  if (n_slots) *n_slots = ctx->slot_conj.size();
+  if (slot_conj) *slot_conj = slot_map(ctx).data();
+  if (n_slots) *n_slots = slot_map(ctx).size();
   return GPC_OK;
 }
 
@@ -2197,7 +2274,8 @@ int gpc_reset_counters(gpc_ctx* ctx) {
 int gpc_metrics(gpc_ctx* ctx, gpc_rule_metric* out, size_t cap, size_t* n) {
   if (!ctx) return -GPC_EINVAL;
   std::lock_guard<std::mutex> g(ctx->ctl);
-  std::vector<unsigned long long> h(ctx->slot_conj.size() * kCounterWords, 0), part(h.size());
+  const std::vector<uint32_t>& conj = slot_map(ctx);
+  std::vector<unsigned long long> h(conj.size() * kCounterWords, 0), part(h.size());
   for (DevState& D : ctx->dev) {
     if (int rc = fold_counters(D)) return rc;
     if (!D.d_counters || h.empty()) continue;
@@ -2207,10 +2285,10 @@ int gpc_metrics(gpc_ctx* ctx, gpc_rule_metric* out, size_t cap, size_t* n) {
     for (size_t i = 0; i < h.size(); i++) h[i] += part[i];
   }
   size_t k = 0;
-  for (size_t s = 0; s < ctx->slot_conj.size(); s++) {
-    if (!ctx->slot_conj[s]) continue;
+  for (size_t s = 0; s < conj.size(); s++) {
+    if (!conj[s]) continue;
     if (out && k < cap) {
-      out[k].conj_id = ctx->slot_conj[s];
+      out[k].conj_id = conj[s];
       out[k].reserved = 0;
       out[k].packets = h[kCounterWords * s];
       out[k].bytes = h[kCounterWords * s + 1];
@@ -2251,7 +2329,7 @@ int gpc_get_image_stats(gpc_ctx* ctx, gpc_image_stats* out) {
     out->n_hard[i] = ctx->last.n_hard[i];
   }
   out->n_flows = ctx->last.n_flows;
-  out->n_counter_slots = uint32_t(ctx->slot_conj.size());
+  out->n_counter_slots = uint32_t(slot_map(ctx).size());
   out->bytes_records = ctx->last.bytes_records;
   out->bytes_ext = ctx->last.bytes_ext;
   out->bytes_bucket_offsets = ctx->last.bytes_bucket_offsets;
@@ -2411,6 +2489,7 @@ int gpc_debug_epoch6(gpc_ctx* ctx, const uint32_t** pool, size_t* pool_words, ui
 static int commit_impl(gpc_ctx* ctx, bool force_full) {
   if (!ctx) return -GPC_EINVAL;
   std::lock_guard<std::mutex> g(ctx->ctl);
+  PointScope points(ctx);
   FeatureNP::Dirty dirty = ctx->np.take_dirty();
   using clk = std::chrono::steady_clock;
   const clk::time_point tc0 = clk::now();
@@ -2499,6 +2578,7 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
       const clk::time_point tg = clk::now();
       if (ctx->journal.rebuild(ctx->np, ctx->slots, &err) == GPC_OK) {
         pool_gc = true;
+        ctx->pool_unpublished = true;
         ctx->n_pool_gc++;
         if (std::getenv("GPC_COMPACT_DEBUG"))
           std::fprintf(stderr, "commit %llu: pool collection %.1f -> %.1f MB in %.1f ms (%zu live rules, %u extended)\n",
@@ -2594,8 +2674,7 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
     }
     v6_changed = true;
   }
-  const bool svc_changed = ctx->svc.generation() != ctx->svc_gen;
-  if (svc_changed) {
+  if (ctx->svc.generation() != ctx->svc_gen) {
     std::string err;
     std::vector<uint32_t> sb, sb6;
     if (!ctx->svc.empty() && (rc = ctx->svc.build_image(&sb, &err))) return rc;
@@ -2603,7 +2682,11 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
     ctx->svc_blob = std::move(sb);
     ctx->svc6_blob = std::move(sb6);
     ctx->svc_gen = ctx->svc.generation();
+    ctx->svc_unpublished = true;
   }
+  // (unpublished: built by this commit, or by an earlier one that failed before its publish; the
+  // device slots then still hold the image before it, or none after a gpc_replay that failed)
+  const bool svc_changed = ctx->svc_unpublished;
   // the packet-in image follows the realized flows, not the image build: rebuilt only when a flow
   // loading PacketInOperationField came, went or changed (no work per flow otherwise)
   if (ctx->np.pin_generation() != ctx->pin_gen) {
@@ -2621,7 +2704,7 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
     }
   }
   const bool pin_changed = ctx->pin_unpublished;
-  ctx->slot_conj = ctx->slots.slot_conj();
+  ctx->slot_conj_next = ctx->slots.slot_conj();  // slot_conj itself changes at publish: the device counts for the old epoch until then
   if (full) ctx->n_full++;
   else ctx->n_delta++;
   // The new epoch goes to every device slot: uploads on each slot's stream, one synchronize per
@@ -2658,14 +2741,16 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
       ne[k].base = std::move(bg_base[k]);
       ne[k].pool = std::move(bg_pool[k]);
     } else if (full || installed || resync4 || !D.cur.base) {
-      if ((rc = upload_image(ctx->last, D.device, us, &ne[k].base, &ctx->fail_uploads))) return fail(rc);
+      if ((rc = upload_image(ctx->last, D.device, us, &ne[k].base, ctx))) return fail(rc);
     } else {
       ne[k].base = D.cur.base;
-      ne[k].pool = pool_gc ? nullptr : D.cur.pool;  // (a collected pool: a fresh one, uploaded whole)
+      // (a collected pool: a fresh one, uploaded whole -- also when the collecting commit failed: the
+      // published epoch's launches still read the old pool, which the rewritten journal must not overwrite)
+      ne[k].pool = ctx->pool_unpublished ? nullptr : D.cur.pool;
     }
     ne[k].base_gen = ctx->gen4;
     if (jn.active() && !ne[k].pool) {  // the journal pool of a new base is allocated on first use
-      if ((rc = alloc_pool(D.device, us, &ne[k].pool))) return fail(rc);
+      if ((rc = alloc_pool(D.device, us, &ne[k].pool, ctx))) return fail(rc);
       new_pool = true;
     }
   }
@@ -2688,7 +2773,7 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
       ctx->stage = nullptr;
       ctx->stage_bytes = 0;
       const size_t cap = std::max(2 * copy_bytes, size_t(16) << 20);
-      if (hip_ok(hipHostMalloc(&ctx->stage, cap, hipHostMallocPortable))) return fail(-GPC_EDEV);
+      if (dev_point(ctx) || hip_ok(hipHostMalloc(&ctx->stage, cap, hipHostMallocPortable))) return fail(-GPC_EDEV);
       ctx->stage_bytes = cap;
     }
     std::memcpy(ctx->stage, jn.pool.data() + jn.uploaded, tail_bytes);
@@ -2711,6 +2796,10 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
   if (ctx->cfg.ipv6_enabled && !v6_full && !ctx->last6.blob.empty())
     for (size_t k = 0; k < nd; k++) resync6 |= !ctx->dev[k].cur.v6 || ctx->dev[k].cur.v6_gen != ctx->gen6;
   if (resync6) v6_changed = true;
+  // a slot still publishing an older IPv6 journal header (the commit that appended the latest one
+  // failed before its publish): this commit sends the tail and switches the header, rules changed or not
+  if (ctx->cfg.ipv6_enabled && !v6_full && j6.active())
+    for (size_t k = 0; k < nd; k++) v6_changed |= ctx->dev[k].cur.v6 && ctx->dev[k].cur.v6_jhdr != j6.hdr_off;
   const bool j6_active = v6_changed && !v6_full && j6.active();
   if (j6_active && (resync6 || !ctx->dev[0].cur.v6_pool)) j6.uploaded = 0;
   const size_t j6_from = j6.uploaded;
@@ -2724,7 +2813,7 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
       ctx->stage6 = nullptr;
       ctx->stage6_bytes = 0;
       const size_t cap = std::max(2 * copy6_bytes, size_t(16) << 20);
-      if (hip_ok(hipHostMalloc(&ctx->stage6, cap, hipHostMallocPortable))) return fail(-GPC_EDEV);
+      if (dev_point(ctx) || hip_ok(hipHostMalloc(&ctx->stage6, cap, hipHostMallocPortable))) return fail(-GPC_EDEV);
       ctx->stage6_bytes = cap;
     }
     std::memcpy(ctx->stage6, j6.pool.data() + j6.uploaded, t6);
@@ -2735,16 +2824,18 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
     DevState& D = ctx->dev[k];
     hipStream_t us = D.ustream;
     if (hip_ok(hipSetDevice(D.device))) return fail(-GPC_EDEV);
-    if (tail && hip_ok(hipMemcpyAsync(ne[k].pool->d_blob + jn.uploaded, ctx->stage, copy_bytes, hipMemcpyHostToDevice, us)))
+    if (tail && (dev_point(ctx) ||
+                 hip_ok(hipMemcpyAsync(ne[k].pool->d_blob + jn.uploaded, ctx->stage, copy_bytes, hipMemcpyHostToDevice, us))))
       return fail(-GPC_EDEV);
     ne[k].jhdr = jhdr;
     ne[k].jmode = jhdr ? jn.mode() : kModeBase;
     if (resync6) {  // the current host IPv6 base, then the whole journal into a fresh pool
-      if ((rc = upload_image(ctx->last6, D.device, us, &ne[k].v6, &ctx->fail_uploads))) return fail(rc);
+      if ((rc = upload_image(ctx->last6, D.device, us, &ne[k].v6, ctx))) return fail(rc);
       ne[k].v6_lpm = ctx->last6.hdr.v6_lpm;
       if (j6_active) {
-        if ((rc = alloc_pool(D.device, us, &ne[k].v6_pool))) return fail(rc);
-        if (tail6 && hip_ok(hipMemcpyAsync(ne[k].v6_pool->d_blob, ctx->stage6, copy6_bytes, hipMemcpyHostToDevice, us)))
+        if ((rc = alloc_pool(D.device, us, &ne[k].v6_pool, ctx))) return fail(rc);
+        if (tail6 && (dev_point(ctx) ||
+                      hip_ok(hipMemcpyAsync(ne[k].v6_pool->d_blob, ctx->stage6, copy6_bytes, hipMemcpyHostToDevice, us))))
           return fail(-GPC_EDEV);
         ne[k].v6_jhdr = ctx->journal6.hdr_off;
       }
@@ -2757,25 +2848,25 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
       ne[k].v6_gen = D.cur.v6_gen;
       if (v6_changed && ne[k].v6) {
         if (j6_active && !ne[k].v6_pool) {
-          if ((rc = alloc_pool(D.device, us, &ne[k].v6_pool))) return fail(rc);
+          if ((rc = alloc_pool(D.device, us, &ne[k].v6_pool, ctx))) return fail(rc);
         }
-        if (tail6 && hip_ok(hipMemcpyAsync(ne[k].v6_pool->d_blob + j6_from, ctx->stage6, copy6_bytes,
-                                           hipMemcpyHostToDevice, us)))
+        if (tail6 && (dev_point(ctx) || hip_ok(hipMemcpyAsync(ne[k].v6_pool->d_blob + j6_from, ctx->stage6, copy6_bytes,
+                                                              hipMemcpyHostToDevice, us))))
           return fail(-GPC_EDEV);
         ne[k].v6_jhdr = j6_active ? ctx->journal6.hdr_off : 0u;
       }
     } else if (!ctx->last6.blob.empty()) {
-      if ((rc = upload_image(ctx->last6, D.device, us, &ne[k].v6, &ctx->fail_uploads))) return fail(rc);
+      if ((rc = upload_image(ctx->last6, D.device, us, &ne[k].v6, ctx))) return fail(rc);
       ne[k].v6_lpm = ctx->last6.hdr.v6_lpm;
       ne[k].v6_gen = ctx->gen6;
     }
     if (!svc_changed) ne[k].svc = D.cur.svc, ne[k].svc6 = D.cur.svc6;
-    else if (!ctx->svc_blob.empty() && (rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc))) return fail(rc);
+    else if (!ctx->svc_blob.empty() && (rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc, ctx))) return fail(rc);
     if (svc_changed && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
-    if (svc_changed && !ctx->svc6_blob.empty() && (rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6))) return fail(rc);
+    if (svc_changed && !ctx->svc6_blob.empty() && (rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6, ctx))) return fail(rc);
     if (svc_changed && ne[k].svc6) ne[k].svc6->affinity = svc_has_affinity(ctx->svc6_blob);
     if (!pin_changed) ne[k].pin = D.cur.pin;
-    else if (!ctx->pin_blob.empty() && (rc = upload_words(ctx->pin_blob, D.device, us, &ne[k].pin))) return fail(rc);
+    else if (!ctx->pin_blob.empty() && (rc = upload_words(ctx->pin_blob, D.device, us, &ne[k].pin, ctx))) return fail(rc);
     ne[k].epoch = epoch;
     // counters: grow to the slot count, zero released slots (their Metric flows were deleted)
     nc[k] = D.d_counters;
@@ -2786,17 +2877,19 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
       new_copies[k] = counter_copies_for(new_cap[k]);
       const size_t bytes = new_cap[k] * kCounterBytes * (new_copies[k] + 1);
       nc[k] = nullptr;
-      if (hip_ok(hipMalloc(&nc[k], bytes)) || hip_ok(hipMemset(nc[k], 0, bytes))) return fail(-GPC_EDEV);
+      if (dev_point(ctx) || hip_ok(hipMalloc(&nc[k], bytes)) || dev_point(ctx) || hip_ok(hipMemset(nc[k], 0, bytes)))
+        return fail(-GPC_EDEV);
     }
   }
   const clk::time_point tc2 = clk::now();
   for (size_t k = 0; k < nd; k++)  // the new epoch is resident on every slot before it is published
-    if (hip_ok(hipSetDevice(ctx->dev[k].device)) || hip_ok(hipStreamSynchronize(ctx->dev[k].ustream)))
+    if (hip_ok(hipSetDevice(ctx->dev[k].device)) || dev_point(ctx) || hip_ok(hipStreamSynchronize(ctx->dev[k].ustream)))
       return fail(-GPC_EDEV);
   const clk::time_point tc3 = clk::now();
   if (tail) jn.uploaded = jn.pool.size();
   if (tail6) j6.uploaded = j6.pool.size();
-  ctx->pin_unpublished = false;
+  ctx->pin_unpublished = ctx->svc_unpublished = ctx->pool_unpublished = false;
+  ctx->slot_conj = ctx->slot_conj_next;
   ctx->epoch = epoch;
   std::vector<DevEpoch> old(nd);
   std::vector<unsigned long long*> old_counters(nd, nullptr);

@@ -170,7 +170,8 @@ EXPORTS = ["gpc_create", "gpc_destroy", "gpc_initialize", "gpc_install_rule", "g
            "gpc_affinity_stats6", "gpc_debug_affinity_table6", "gpc_debug_set_affinity_seq6",
            "gpc_debug_set_affinity6_digest_bits", "gpc_debug_counter_layout", "gpc_trace_on", "gpc_trace6",
            "gpc_debug_v6_prefix_of_code", "gpc_pin_scratch_bytes", "gpc_classify_pin_on", "gpc_classify6_pin_on",
-           "gpc_classify_host_pin_on", "gpc_classify6_host_pin", "gpc_debug_pin_image"]
+           "gpc_classify_host_pin_on", "gpc_classify6_host_pin", "gpc_debug_pin_image",
+           "gpc_debug_fail_upload_at", "gpc_debug_upload_points"]
 
 _lib = None
 
@@ -193,6 +194,8 @@ def load(path: str = LIB_PATH):
                                     C.POINTER(sz)]
     lib.gpc_destroy.argtypes = [vp]
     lib.gpc_debug_fail_uploads.argtypes = [vp, C.c_int]
+    lib.gpc_debug_fail_upload_at.argtypes = [vp, C.c_int]
+    lib.gpc_debug_upload_points.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.gpc_destroy.restype = None
     lib.gpc_initialize.argtypes = [vp]
     lib.gpc_install_rule.argtypes = [vp, C.POINTER(gpc_rule)]
@@ -743,6 +746,17 @@ class Classifier:
     def debug_fail_uploads(self, n):
         """Fault injection (tests): the next n device image uploads fail with GPC_EDEV."""
         _check(self.lib.gpc_debug_fail_uploads(self.h, int(n)), "gpc_debug_fail_uploads")
+
+    def debug_fail_upload_at(self, skip):
+        """Fault injection (tests): the (skip+1)-th device allocation, copy or synchronize of the next
+        commit / compact / replay fails with GPC_EDEV, once; skip < 0 disarms."""
+        _check(self.lib.gpc_debug_fail_upload_at(self.h, int(skip)), "gpc_debug_fail_upload_at")
+
+    def debug_upload_points(self) -> int:
+        """The number of such points the last commit / compact / replay passed."""
+        n = C.c_uint32()
+        _check(self.lib.gpc_debug_upload_points(self.h, C.byref(n)), "gpc_debug_upload_points")
+        return n.value
 
     def classify_host(self, cols: Dict[str, np.ndarray], count=False, lb=False, slot=0):
         """Verdicts (n, 2); with lb=True also the Service stage results (n,) of LB_DTYPE."""

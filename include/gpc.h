@@ -520,13 +520,24 @@ int gpc_dump_groups(gpc_ctx* ctx, char* buf, size_t cap, size_t* needed);
  * delta epoch: cost proportional to the changed rules). A background compactor rebuilds the base
  * once compact_after rules are extended or journaled; past max(16384, base rules / 4) live journal
  * rules without one the whole image is rebuilt inline. Launches already queued keep the epoch they
- * were launched with. */
+ * were launched with.
+ * On an error (a device allocation, copy or synchronize failed: -GPC_EDEV) nothing is published: every
+ * slot keeps serving the epoch it had, with that epoch's Service and packet-in images, and
+ * gpc_counters / gpc_metrics / gpc_image_stats.epoch keep describing that epoch (counter slots
+ * released by the failed commit are zeroed, and may change owner, only at the next publish). The
+ * host state keeps the new build. The next successful gpc_commit (with or without further changes),
+ * gpc_compact or gpc_replay publishes it whole: bases and journals the slots do not hold, the
+ * Service, IPv6-Service and packet-in images, and a counter array for every slot. */
 int gpc_commit(gpc_ctx* ctx);
 /* Same, but always rebuilds the whole image (compaction: empties the overlay). */
 int gpc_compact(gpc_ctx* ctx);
 /* ReplayFlows (client.go:1130-1152) for the device: rebuilds every device buffer of the current
  * epoch from the host shadow state (after a device reset); flows, conj ids and counter slots are
- * unchanged, device counters restart from zero. */
+ * unchanged, device counters restart from zero. The session-affinity tables are lost.
+ * The old device state is dropped first. On an error after that no slot publishes anything:
+ * gpc_classify* return -GPC_EINVAL, gpc_debug_counter_layout reports capacity 0 and gpc_metrics
+ * zeros, until a later gpc_replay, gpc_commit (also with nothing pending) or gpc_compact rebuilds
+ * every slot: bases, journals, Service and packet-in images, and zeroed counters. */
 int gpc_replay(gpc_ctx* ctx);
 /* Largest batch of one gpc_classify* call (the launch grid is limited to 2^32 work-items). */
 #define GPC_MAX_BATCH (4294967296ull - 256ull)
@@ -765,6 +776,17 @@ int gpc_debug_epoch6(gpc_ctx* ctx, const uint32_t** pool, size_t* pool_words, ui
  * build, and the next successful commit re-uploads every base the device slots do not hold
  * (tests/test_gpu_ipv6_delta.py). */
 int gpc_debug_fail_uploads(gpc_ctx* ctx, int n);
+/* Test hook (fault injection at every point). A "point" is one device allocation, copy or
+ * synchronize of gpc_commit / gpc_compact / gpc_replay, in program order over the slots: each base,
+ * Service, IPv6-Service and packet-in image upload, each journal pool allocation, each journal tail
+ * copy, each growth of a pinned staging buffer, the counter array's allocation and its clearing, and
+ * the per-slot synchronize before the publish (not the background compactor's uploads). The
+ * (skip+1)-th point passed by this context's next such call returns -GPC_EDEV before the device call
+ * is made; the hook then disarms itself (also when that call passes fewer points). skip < 0 disarms. */
+int gpc_debug_fail_upload_at(gpc_ctx* ctx, int skip);
+/* The number of points the context's last gpc_commit / gpc_compact / gpc_replay passed (a failed
+ * one: up to and including the point that failed). */
+int gpc_debug_upload_points(gpc_ctx* ctx, uint32_t* n);
 /* The epoch (gpc_image_stats.epoch) the last gpc_classify* launch on `stream` was bound to: with
  * classification concurrent to commits, every launch sees exactly this one committed epoch. */
 int gpc_stream_epoch(gpc_ctx* ctx, void* stream, uint64_t* epoch);

@@ -100,6 +100,7 @@ struct DevImage {  // one uploaded image (freed when the last epoch using it ret
   uint32_t axes = 0;                    // axes read by the sub-indexes (group_axes)
   bool composite = false;               // some table has a composite driver index (TableHdr n_cidx)
   bool affinity = false;                // a Service image with session-affinity Services (SvcHdr n_aff)
+  bool short_circuit = false;           // a Service image with short-circuit Services (SvcHdr n_sc)
   // an IPv6 base: the prefix tree its codes come from (gpc_trace6 translates a slot's codes through
   // the tree of the base that slot publishes; the host image may be a newer build whose upload failed)
   std::shared_ptr<V6Codes> codes6;
@@ -576,6 +577,14 @@ static int upload_words(const std::vector<uint32_t>& w, int device, hipStream_t 
 static bool svc_has_affinity(const std::vector<uint32_t>& blob) {
   return blob.size() * 4 >= sizeof(SvcHdr) && reinterpret_cast<const SvcHdr*>(blob.data())->n_aff != 0;
 }
+static bool svc_has_short_circuit(const std::vector<uint32_t>& blob) {
+  return blob.size() * 4 >= sizeof(SvcHdr) && reinterpret_cast<const SvcHdr*>(blob.data())->n_sc != 0;
+}
+// The batch as the launches read it. gpc_pkt_soa.source is the struct's last member and is read only
+// in a gpc_config.packet_source context (a caller compiled against the shorter struct stays valid);
+// the launches get the column only when the bound Service image `svc` holds a short-circuit Service --
+// any other batch takes exactly the loads it took before.
+static gpc_pkt_soa batch_columns(const gpc_ctx* ctx, const gpc_pkt_soa* pk, const DevImage* svc);
 
 // The packet-in image (core.hpp PinHdr) of conj id -> PacketInOperationField; empty map: no image.
 // Each id goes to the emptier of its two buckets; the table doubles until every id has a slot.
@@ -1278,8 +1287,10 @@ int gpc_replay(gpc_ctx* ctx) {
     }
     if (!rc && !ctx->svc_blob.empty()) rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc, ctx);
     if (!rc && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
+    if (!rc && ne[k].svc) ne[k].svc->short_circuit = svc_has_short_circuit(ctx->svc_blob);
     if (!rc && !ctx->svc6_blob.empty()) rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6, ctx);
     if (!rc && ne[k].svc6) ne[k].svc6->affinity = svc_has_affinity(ctx->svc6_blob);
+    if (!rc && ne[k].svc6) ne[k].svc6->short_circuit = svc_has_short_circuit(ctx->svc6_blob);
     if (!rc && !ctx->pin_blob.empty()) rc = upload_words(ctx->pin_blob, D.device, us, &ne[k].pin, ctx);
     if (!rc && (dev_point(ctx) || hip_ok(hipMalloc(&nc[k], cap * kCounterBytes * (copies + 1))) || dev_point(ctx) ||
                 hip_ok(hipMemset(nc[k], 0, cap * kCounterBytes * (copies + 1)))))
@@ -1659,6 +1670,14 @@ int gpc_debug_set_affinity6_digest_bits(gpc_ctx* ctx, uint32_t slot, uint32_t bi
   return GPC_OK;
 }
 
+static gpc_pkt_soa batch_columns(const gpc_ctx* ctx, const gpc_pkt_soa* pk, const DevImage* svc) {
+  static_assert(offsetof(gpc_pkt_soa, source) + sizeof(void*) == sizeof(gpc_pkt_soa), "source is the last member");
+  gpc_pkt_soa b{};
+  std::memcpy(&b, pk, offsetof(gpc_pkt_soa, source));
+  if (ctx->cfg.packet_source && svc && svc->short_circuit) b.source = pk->source;
+  return b;
+}
+
 int gpc_classify(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, int32_t count, void* stream) {
   return gpc_classify_on(ctx, 0, pk, n, out, nullptr, count, stream);
 }
@@ -1696,8 +1715,9 @@ static int pin_collect(const DevState& D, const gpc_pin_queue* q, const gpc_verd
 }
 
 // gpc_classify_on, with an optional packet-in queue (null: exactly the launches of a call without one).
-static int classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result* lb_out,
+static int classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* caller_pk, size_t n, gpc_verdict* out, gpc_lb_result* lb_out,
                        const gpc_pin_queue* q, int32_t count, void* stream) {
+  const gpc_pkt_soa* pk = caller_pk;
   if (!ctx || !pk || (!out && n) || n > GPC_MAX_BATCH || slot >= ctx->dev.size()) return -GPC_EINVAL;
   if (n && (!pk->src || !pk->dst || !pk->sport || !pk->dport || !pk->proto || !pk->out_port)) return -GPC_EINVAL;
   if (q && pin_queue_check(q, n)) return -GPC_EINVAL;
@@ -1706,6 +1726,8 @@ static int classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_
   const auto d = launch_lock(ctx->data, ctx->publishers);
   DevState& D = ctx->dev[slot];
   if (!D.cur.base) return -GPC_EINVAL;  // nothing committed yet
+  const gpc_pkt_soa batch = batch_columns(ctx, caller_pk, D.cur.svc.get());
+  pk = &batch;
   const bool jpool = D.cur.jhdr && D.cur.jmode != kModeBase;
   EpochArgs ep{D.cur.base->d_hdr, D.cur.base->d_blob, jpool ? D.cur.pool->d_blob : nullptr, D.cur.jhdr,
                D.cur.svc ? D.cur.svc->d_blob : nullptr, 0u, {D.cur.base->sort_table[0], D.cur.base->sort_table[1]},
@@ -1729,6 +1751,7 @@ static int classify_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_
   if (affinity) {
     shape.ct_dst = shape.svc_group = pk->src;
     shape.dest = reinterpret_cast<const uint8_t*>(pk->src);
+    shape.source = nullptr;  // read by the Service stage in front, at caller indexes
     ga.lb = 0;  // the LB results are stored at caller indexes by aff_resolve_kernel
   }
   uint8_t* scratch = nullptr;
@@ -1805,7 +1828,8 @@ int gpc_trace_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict
                 {pk->tun_id, 4, (const void**)&d.tun_id},     {pk->ct_src, 4, (const void**)&d.ct_src},
                 {pk->ct_dst, 4, (const void**)&d.ct_dst},     {pk->ct_state, 1, (const void**)&d.ct_state},
                 {pk->dest, 1, (const void**)&d.dest},         {pk->len, 2, (const void**)&d.len},
-                {pk->ct_mark, 1, (const void**)&d.ct_mark}};
+                {pk->ct_mark, 1, (const void**)&d.ct_mark},
+                {ctx->cfg.packet_source ? pk->source : nullptr, 1, (const void**)&d.source}};  // (read under the gate alone)
   constexpr size_t kSlot = 16, kOut = 512;  // column slots, then verdicts / LB result / steps / count
   const size_t ncol = sizeof cols / sizeof cols[0];
   std::vector<uint8_t> h(kOut + ncol * kSlot, 0);
@@ -1829,6 +1853,7 @@ int gpc_trace_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict
       EpochArgs ep{cur.base->d_hdr, cur.base->d_blob, cur.jhdr ? cur.pool->d_blob : nullptr, cur.jhdr,
                    cur.svc ? cur.svc->d_blob : nullptr, 0u, {0, 0}, 0u, 0u};
       DevState& D = ctx->dev[slot];
+      if (!(cur.svc && cur.svc->short_circuit)) d.source = nullptr;  // as a batch: only against such an image
       uint8_t* ascr = nullptr;
       bool noep = false;
       // Session affinity with a table in use: the Service stage runs read-only over the table
@@ -1902,7 +1927,8 @@ int gpc_trace6(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict* 
                 {pk->in_port, 4, (const void**)&d.in_port},   {pk->svc_group, 4, (const void**)&d.svc_group},
                 {pk->tun_id, 4, (const void**)&d.tun_id},     {pk->ct_state, 1, (const void**)&d.ct_state},
                 {pk->dest, 1, (const void**)&d.dest},         {pk->len, 2, (const void**)&d.len},
-                {pk->ct_mark, 1, (const void**)&d.ct_mark}};
+                {pk->ct_mark, 1, (const void**)&d.ct_mark},
+                {ctx->cfg.packet_source ? pk->source : nullptr, 1, (const void**)&d.source}};  // (read under the gate alone)
   // outputs: verdicts [0, 16), LB result [16, 48), codes and their bits [48, 80), step count [80, 84), steps [96, ..)
   constexpr size_t kSlot = 16, kLb = 16, kCodes = 48, kCount = 80, kSteps = 96, kOut = 512;
   static_assert(kSteps + kMaxTraceSteps * sizeof(TraceStep) <= kOut, "the steps fit in front of the column slots");
@@ -1925,6 +1951,7 @@ int gpc_trace6(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, gpc_verdict* 
                  nullptr, cur.v6_lpm, {0, 0}, 0u, 0u};
     Trace6Args t{};
     t.svc6 = cur.svc6 ? cur.svc6->d_blob : nullptr;
+    if (!(cur.svc6 && cur.svc6->short_circuit)) d.source = nullptr;  // as a batch: only against such an image
     t.out = reinterpret_cast<uint4*>(buf);
     t.lb_out = reinterpret_cast<uint4*>(buf + kLb);
     t.codes = reinterpret_cast<uint32_t*>(buf + kCodes);
@@ -1990,8 +2017,9 @@ int gpc_classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t 
 }
 
 // gpc_classify6_lb_on, with an optional packet-in queue (null: exactly the launches of a call without one).
-static int classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
+static int classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* caller_pk, size_t n, gpc_verdict* out, gpc_lb_result6* lb_out,
                         const gpc_pin_queue* q, int32_t count, void* stream) {
+  const gpc_pkt_soa* pk = caller_pk;
   static_assert(sizeof(gpc_lb_result6) == 32, "two 128-bit stores per packet (classify.hip v6_lb_kernel)");
   if (reinterpret_cast<uintptr_t>(lb_out) % 16) return -GPC_EINVAL;
   if (q && pin_queue_check(q, n)) return -GPC_EINVAL;
@@ -2004,6 +2032,8 @@ static int classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size
   const auto d = launch_lock(ctx->data, ctx->publishers);
   DevState& D = ctx->dev[slot];
   if (!D.cur.v6) return -GPC_EINVAL;  // IPv6 disabled or nothing committed yet
+  const gpc_pkt_soa batch = batch_columns(ctx, caller_pk, D.cur.svc6.get());
+  pk = &batch;
   EpochArgs ep{D.cur.v6->d_hdr, D.cur.v6->d_blob, D.cur.v6_jhdr ? D.cur.v6_pool->d_blob : nullptr, D.cur.v6_jhdr,
                nullptr, D.cur.v6_lpm, {0, 0}, uint32_t(D.counter_cap * kCounterWords), D.counter_copies - 1};
   hipStream_t st = (hipStream_t)stream;
@@ -2021,6 +2051,7 @@ static int classify6_on(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, size
   shape.src = shape.dst = reinterpret_cast<const uint32_t*>(pk->src6);
   shape.ct_src = pk->ct_src6 ? shape.src : nullptr;
   shape.ct_dst = pk->ct_dst6 || svc6 ? shape.src : nullptr;
+  shape.source = nullptr;  // read by the Service stage in front, at caller indexes
   if (svc6) {
     shape.svc_group = shape.src;
     shape.dest = pk->src6;
@@ -2136,6 +2167,7 @@ static int classify6_host(gpc_ctx* ctx, const gpc_pkt_soa* pk, size_t n, gpc_ver
   up(pk->dest, 1, (const void**)&d.dest);
   up(pk->len, 2, (const void**)&d.len);
   up(pk->ct_mark, 1, (const void**)&d.ct_mark);
+  if (ctx->cfg.packet_source) up(pk->source, 1, (const void**)&d.source);
   void* dout = nullptr;
   void* dlb = nullptr;
   if (!rc && hip_ok(hipMalloc(&dout, n * 2 * sizeof(gpc_verdict)))) rc = -GPC_EDEV;
@@ -2206,6 +2238,7 @@ static int classify_host(gpc_ctx* ctx, uint32_t slot, const gpc_pkt_soa* pk, siz
   up(pk->dest, 1, (const void**)&d.dest);
   up(pk->len, 2, (const void**)&d.len);
   up(pk->ct_mark, 1, (const void**)&d.ct_mark);
+  if (ctx->cfg.packet_source) up(pk->source, 1, (const void**)&d.source);
   void* dout = nullptr;
   void* dlb = nullptr;
   if (!rc && hip_ok(hipMalloc(&dout, n * 2 * sizeof(gpc_verdict)))) rc = -GPC_EDEV;
@@ -2863,8 +2896,10 @@ static int commit_impl(gpc_ctx* ctx, bool force_full) {
     if (!svc_changed) ne[k].svc = D.cur.svc, ne[k].svc6 = D.cur.svc6;
     else if (!ctx->svc_blob.empty() && (rc = upload_words(ctx->svc_blob, D.device, us, &ne[k].svc, ctx))) return fail(rc);
     if (svc_changed && ne[k].svc) ne[k].svc->affinity = svc_has_affinity(ctx->svc_blob);
+    if (svc_changed && ne[k].svc) ne[k].svc->short_circuit = svc_has_short_circuit(ctx->svc_blob);
     if (svc_changed && !ctx->svc6_blob.empty() && (rc = upload_words(ctx->svc6_blob, D.device, us, &ne[k].svc6, ctx))) return fail(rc);
     if (svc_changed && ne[k].svc6) ne[k].svc6->affinity = svc_has_affinity(ctx->svc6_blob);
+    if (svc_changed && ne[k].svc6) ne[k].svc6->short_circuit = svc_has_short_circuit(ctx->svc6_blob);
     if (!pin_changed) ne[k].pin = D.cur.pin;
     else if (!ctx->pin_blob.empty() && (rc = upload_words(ctx->pin_blob, D.device, us, &ne[k].pin, ctx))) return fail(rc);
     ne[k].epoch = epoch;

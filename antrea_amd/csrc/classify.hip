@@ -121,7 +121,11 @@ struct V6LbArgs {
   uint32_t *out_port_out, *svc_group_out;
   uint8_t* dest_out;
   uint4* lb_out;  // two per packet; may be null
+  const uint8_t* source;  // gpc_source, optional: set only against an image with short-circuit Services
 };
+// kSrc: the batch has the packet source column and the image a short-circuit Service (a.source set);
+// without it the source is the constant UNKNOWN and the step to the Cluster record folds away.
+template <bool kSrc>
 __global__ __launch_bounds__(kLbBlock) void v6_lb_kernel(V6LbArgs a, uint64_t n) {
   const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
   if (i >= n) return;
@@ -132,6 +136,7 @@ __global__ __launch_bounds__(kLbBlock) void v6_lb_kernel(V6LbArgs a, uint64_t n)
   uint32_t out_port = a.out_port[i];
   uint32_t svc_group = a.svc_group ? a.svc_group[i] : 0u;
   uint32_t dest = a.dest ? a.dest[i] : 0u;
+  const uint32_t source = kSrc ? uint32_t(a.source[i]) : uint32_t(GPC_SOURCE_UNKNOWN);  // (with the other optional columns)
   uint32_t lb[8];
   const uint32_t f = lb_stage6(
       a.svc,
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(kLbBlock) void v6_lb_kernel(V6LbArgs a, uint64_t n)
         return Svc6Src{__builtin_bswap32(s.x) ^ __builtin_bswap32(s.y) ^ __builtin_bswap32(s.z) ^ __builtin_bswap32(s.w),
                        uint32_t(a.sport[i])};
       },
-      dst, dport, proto, svc_group, out_port, dest, lb);
+      dst, dport, proto, svc_group, out_port, dest, lb, source);
   a.dst_out[i] = make_uint4(__builtin_bswap32(dst[0]), __builtin_bswap32(dst[1]), __builtin_bswap32(dst[2]), __builtin_bswap32(dst[3]));
   a.dport_out[i] = uint16_t(dport);
   a.out_port_out[i] = out_port;
@@ -326,6 +331,7 @@ __global__ __launch_bounds__(kGroupThreads) void group_tiles_kernel(EpochArgs ep
   GPC_GROUP_COL(dest, uint8_t);
   GPC_GROUP_COL(len, uint16_t);
   GPC_GROUP_COL(ct_mark, uint8_t);
+  GPC_GROUP_COL(source, uint8_t);
 #undef GPC_GROUP_COL
 }
 
@@ -363,7 +369,7 @@ __device__ __forceinline__ uint64_t logical_block(uint32_t mode) {
 // pkt_lane / pkt_stride: this lane's column of the block's [word][lane] packet table in LDS.
 // kRes: the Service stage already ran (v6_lb_kernel): the columns are the rewritten ones and bit
 // kDestNoEndpoint of `dest` marks a packet of a Service without Endpoints.
-template <int kDelta, bool kSvc, int kStage, bool kRes = false>
+template <int kDelta, int kSvc, int kStage, bool kRes = false>
 __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t i, uint4* __restrict__ out,
                                              uint4* __restrict__ lb_out, unsigned long long* __restrict__ counters, int count,
                                              const uint32_t* __restrict__ orig, uint2* __restrict__ mid,
@@ -411,6 +417,13 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
   // parked in the lane's LDS column below, not held in a register over a walk.
   uint32_t len = (count && pk.len) ? uint32_t(pk.len[i]) : 0u;
   const uint32_t ct_state = pk.ct_state ? pk.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK);
+  // The packet source, in the same round. kSvc == 2: the batch has the column and the bound Service
+  // image holds a short-circuit Service (decided by the host from the header, per launch); any other
+  // batch runs the instantiation in which the source is the constant UNKNOWN, so lb_stage's step to
+  // the Cluster record folds away and the code is the one of a library without the column. The
+  // ingress launch reads what the Service stage made of it from park[].
+  uint32_t source = GPC_SOURCE_UNKNOWN;
+  if constexpr (kSvc == 2 && kStage != 2) source = pk.source[i];
   const uint32_t ct_mark = pk.ct_mark ? pk.ct_mark[i] : 0u;  // (last: its hairpin bit is tested first)
   // Service stage. kStage 0: one launch does it and both policy stages. kStage 1 / 2 (Service
   // batches split like the others): the egress launch runs it and parks the fields it rewrites
@@ -439,7 +452,7 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
     // (read after the egress-action check below)
   } else if (kSvc) {
     uint32_t lb[4];
-    const uint32_t f = lb_stage(ep.svc, src, dst, sport, dport, proto, svc_group, out_port, dest, lb);
+    const uint32_t f = lb_stage(ep.svc, src, dst, sport, dport, proto, svc_group, out_port, dest, lb, source);
     // grouped with the un-permute (gout): results in grouped order, unpermute_kernel stores them
     if (lb_out) lb_out[gout ? i : at(i)] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
     if (kStage == 1) park[i] = make_uint4(dst, (dport & 0xffffu) | (dest << 16), out_port, svc_group);
@@ -576,7 +589,7 @@ __device__ __forceinline__ void classify_one(const EpochArgs& ep, const gpc_pkt_
 }
 
 // kDelta: the epoch mode (core.hpp kModeBase / kModeExt / kModeJournal).
-template <int kDelta, bool kSvc, int kStage, bool kSort = false>
+template <int kDelta, int kSvc, int kStage, bool kSort = false>
 __global__ __launch_bounds__(block_threads<kSort>()) __attribute__((amdgpu_waves_per_eu(kDelta == kModeJournal ? GPC_DELTA_WAVES_PER_EU : kDelta == kModeExt ? GPC_EXT_WAVES_PER_EU : GPC_WAVES_PER_EU))) void classify_kernel(
     EpochArgs ep, gpc_pkt_soa pk, uint64_t n, uint4* __restrict__ out, uint4* __restrict__ lb_out,
     unsigned long long* __restrict__ counters, int count, const uint32_t* __restrict__ orig, uint2* __restrict__ mid,
@@ -713,24 +726,25 @@ static void launch_unpermute(const void* mid, uint32_t mid_words, const uint2* g
                      reinterpret_cast<const uint32_t*>(mid), mid_words, gout, orig, n, out, lbg, lb_out);
 }
 
-template <int kDelta, bool kSvc, bool kRes = false>
+template <int kDelta, int kSvc, bool kRes = false>
 static void launch(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_verdict* out, uint4* lb_out,
                    unsigned long long* counters, int count, const uint32_t* orig, uint2* mid, uint32_t xo, uint2* gout,
                    uint4* park, hipStream_t stream, LaunchMarks* marks) {
   const uint64_t blocks = (n + kBlock - 1) / kBlock;
   uint4* const o = reinterpret_cast<uint4*>(out);
+  constexpr int kS = kSvc ? kSvc : 1;  // 2: the Service stage loads the packet source column (classify_one)
   if (kSvc && park) {  // split like the Service-free batches, the rewritten fields parked in between
     launch_mark(marks, kLaunchEgress, stream);
-    hipLaunchKernelGGL((classify_kernel<kDelta, true, 1>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
+    hipLaunchKernelGGL((classify_kernel<kDelta, kS, 1>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
                        lb_out, counters, count, orig, mid, xo, gout, park);
     launch_mark(marks, kLaunchIngress, stream);
-    hipLaunchKernelGGL((classify_kernel<kDelta, true, 2>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
+    hipLaunchKernelGGL((classify_kernel<kDelta, 1, 2>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
                        lb_out, counters, count, orig, mid, xo, gout, park);
     return;
   }
   if (kSvc) {
     launch_mark(marks, kLaunchBoth, stream);
-    hipLaunchKernelGGL((classify_kernel<kDelta, true, 0>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
+    hipLaunchKernelGGL((classify_kernel<kDelta, kS, 0>), dim3(uint32_t(blocks)), dim3(kBlock), 0, stream, ep, pk, n, o,
                        lb_out, counters, count, orig, mid, xo, gout, nullptr);
     return;
   }
@@ -804,7 +818,8 @@ __global__ void trace_kernel(EpochArgs ep, gpc_pkt_soa pk, uint4* __restrict__ o
   uint32_t lb[4] = {0u, 0u, 0u, 0u};
   *n_steps = 0;
   if (ep.svc) {
-    const uint32_t f = lb_stage(ep.svc, src, dst, sport, dport, proto, svc_group, out_port, dest, lb);
+    const uint32_t f = lb_stage(ep.svc, src, dst, sport, dport, proto, svc_group, out_port, dest, lb,
+                                pk.source ? uint32_t(pk.source[0]) : uint32_t(GPC_SOURCE_UNKNOWN));
     if (f & GPC_LB_NO_ENDPOINT) {
       out[0] = make_uint4(0u, pack_verdict(GPC_ACT_REJECT, GPC_VTABLE_ENDPOINT_DNAT, 0, 0), 0u, 0u);
       lb_out[0] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
@@ -862,11 +877,12 @@ __global__ void trace6_kernel(EpochArgs ep, gpc_pkt_soa pk, Trace6Args t) {
   for (int k = 0; k < 8; k++) t.codes[k] = 0;
   if (t.svc6) {
     if (t.tab.w) {
-      const Aff6Cols cols{pk.src6, pk.dst6, pk.sport, pk.dport, pk.proto, pk.ct_state, 1u};
+      const Aff6Cols cols{pk.src6, pk.dst6, pk.sport, pk.dport, pk.proto, pk.ct_state, 1u, pk.source};
       bool collided;
       f = lb_stage6_aff<true>(t.svc6, t.tab, t.now, 0u, 0u, cols, a[1], dport, proto, svc_group, out_port, dest, lb, &collided);
     } else {
-      f = lb_stage6(t.svc6, [&]() { return Svc6Src{fold6(a[0]), sport}; }, a[1], dport, proto, svc_group, out_port, dest, lb);
+      f = lb_stage6(t.svc6, [&]() { return Svc6Src{fold6(a[0]), sport}; }, a[1], dport, proto, svc_group, out_port, dest, lb,
+                    pk.source ? uint32_t(pk.source[0]) : uint32_t(GPC_SOURCE_UNKNOWN));
     }
     dest &= ~kDestNoEndpoint;
   }
@@ -973,10 +989,10 @@ static_assert(kMaxPackets == GPC_MAX_BATCH, "gpc.h GPC_MAX_BATCH mirrors the lau
 uint64_t group_scratch_bytes(const gpc_pkt_soa& pk, uint64_t n, bool lb) {
   uint64_t per = 4 /*orig*/ + 8 /*mid*/ + 4 + 4 + 2 + 2 + 1 + 4;  // + src dst sport dport proto out_port
   per += (pk.ct_src ? 4 : 0) + (pk.ct_dst ? 4 : 0) + (pk.in_port ? 4 : 0) + (pk.svc_group ? 4 : 0) + (pk.tun_id ? 4 : 0) +
-         (pk.ct_state ? 1 : 0) + (pk.dest ? 1 : 0) + (pk.len ? 2 : 0) + (pk.ct_mark ? 1 : 0);
+         (pk.ct_state ? 1 : 0) + (pk.dest ? 1 : 0) + (pk.len ? 2 : 0) + (pk.ct_mark ? 1 : 0) + (pk.source ? 1 : 0);
   per += 8;  // gout: the ingress halves of the verdict pairs in grouped order (GroupArgs.unpermute)
   if (lb) per += 16;  // lbg: the Service launch's LB results in grouped order
-  return per * n + 22 * 256;  // every region 256-B aligned
+  return per * n + 23 * 256;  // every region 256-B aligned
 }
 
 // Carves the grouped columns, orig and mid out of group->scratch and launches group_tiles_kernel.
@@ -1009,6 +1025,7 @@ static int launch_group(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, 
   if (pk.dest) g->dest = take(n);
   if (pk.len) g->len = reinterpret_cast<const uint16_t*>(take(2 * n));
   if (pk.ct_mark) g->ct_mark = take(n);
+  if (pk.source) g->source = take(n);
   gpc_pkt_soa in = pk;  // the IPv6 address columns are not read (an IPv6 batch comes as code columns)
   in.src6 = in.dst6 = in.ct_src6 = in.ct_dst6 = nullptr;
   if (!group.unpermute) {
@@ -1045,6 +1062,7 @@ int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc
   p4.src = codes;
   p4.dst = codes + n;
   p4.ct_src = p4.ct_dst = nullptr;
+  p4.source = nullptr;  // read by the Service stage alone, at caller indexes
   const uint8_t* ct_dst6 = pk.ct_dst6;
   if (svc6) {  // the Service stage first: the code pass and the policy launches read what it rewrote
     uint8_t* q = lb_scratch;
@@ -1063,6 +1081,7 @@ int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc
     a.out_port = pk.out_port;
     a.svc_group = pk.svc_group;
     a.dest = pk.dest;
+    a.source = pk.source;
     a.dst_out = reinterpret_cast<uint4*>(take(16 * n));
     a.out_port_out = reinterpret_cast<uint32_t*>(take(4 * n));
     a.svc_group_out = reinterpret_cast<uint32_t*>(take(4 * n));
@@ -1073,7 +1092,8 @@ int launch_classify6(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc
       if (const int rc = launch_aff6(a, pk, n, *al, stream, marks)) return rc;
     } else {
       launch_mark(marks, kLaunchV6Lb, stream);
-      hipLaunchKernelGGL(v6_lb_kernel, dim3(uint32_t((n + kLbBlock - 1) / kLbBlock)), dim3(kLbBlock), 0, stream, a, n);
+      if (a.source) hipLaunchKernelGGL(v6_lb_kernel<true>, dim3(uint32_t((n + kLbBlock - 1) / kLbBlock)), dim3(kLbBlock), 0, stream, a, n);
+      else hipLaunchKernelGGL(v6_lb_kernel<false>, dim3(uint32_t((n + kLbBlock - 1) / kLbBlock)), dim3(kLbBlock), 0, stream, a, n);
     }
     cols.c[1] = reinterpret_cast<const uint8_t*>(a.dst_out);
     p4.dport = a.dport_out;
@@ -1129,11 +1149,14 @@ int launch_classify(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, gpc_
   if (resolved && mode == kModeJournal) launch<kModeJournal, false, true>(e, *p, n, out, nullptr, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
   else if (resolved && mode == kModeExt) launch<kModeExt, false, true>(e, *p, n, out, nullptr, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
   else if (resolved) launch<kModeBase, false, true>(e, *p, n, out, nullptr, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
-  else if (mode == kModeJournal && svc) launch<kModeJournal, true>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
+  else if (mode == kModeJournal && svc && p->source) launch<kModeJournal, 2>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
+  else if (mode == kModeJournal && svc) launch<kModeJournal, 1>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
   else if (mode == kModeJournal) launch<kModeJournal, false>(e, *p, n, out, lb_out, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
-  else if (mode == kModeExt && svc) launch<kModeExt, true>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
+  else if (mode == kModeExt && svc && p->source) launch<kModeExt, 2>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
+  else if (mode == kModeExt && svc) launch<kModeExt, 1>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
   else if (mode == kModeExt) launch<kModeExt, false>(e, *p, n, out, lb_out, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
-  else if (svc) launch<kModeBase, true>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
+  else if (svc && p->source) launch<kModeBase, 2>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
+  else if (svc) launch<kModeBase, 1>(e, *p, n, out, lbk, counters, count, orig, mid, xo, gout, park, stream, marks);
   else launch<kModeBase, false>(e, *p, n, out, lb_out, counters, count, orig, mid, xo, gout, nullptr, stream, marks);
   if (gout) launch_unpermute(mid, 2, gout, orig, n, reinterpret_cast<uint4*>(out), svc ? lbg : nullptr, lb_out, stream, marks);
   launch_mark(marks, kLaunchEnd, stream);
@@ -1167,6 +1190,7 @@ struct AffArgs {
   const uint8_t* proto;
   const uint32_t *out_port, *svc_group;  // svc_group, dest, ct_state: optional
   const uint8_t *dest, *ct_state;
+  const uint8_t* source;  // gpc_source, optional: set only against an image with short-circuit Services
   uint32_t* dst_out;
   uint16_t* dport_out;
   uint32_t *out_port_out, *svc_group_out;
@@ -1184,24 +1208,31 @@ __global__ __launch_bounds__(kLbBlock) void aff_sweep_kernel(AffTable t, uint32_
   const uint64_t s = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
   if (s < (uint64_t(1) << t.log2)) aff_sweep_slot<AffOpsDev>(t, uint32_t(s), now, mode);
 }
+// kSrc: as v6_lb_kernel's.
+template <bool kSrc>
 __global__ __launch_bounds__(kLbBlock) void aff_learn_kernel(AffArgs a, uint64_t n) {
   const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
   if (i >= n) return;
+  if (!kSrc) a.source = nullptr;
   a.tab = aff_striped(a.tab);
   aff_learn<AffOpsDev>(a.svc, a.tab, a.now, a.seq, uint32_t(i), a.src[i], a.dst[i], a.dport[i], a.proto[i],
-                       a.ct_state ? a.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK));
+                       a.ct_state ? a.ct_state[i] : uint32_t(GPC_CT_NEW | GPC_CT_TRK),
+                       a.source ? uint32_t(a.source[i]) : uint32_t(GPC_SOURCE_UNKNOWN));
 }
+template <bool kSrc>
 __global__ __launch_bounds__(kLbBlock) void aff_resolve_kernel(AffArgs a, uint64_t n) {
   const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
   if (i >= n) return;
+  if (!kSrc) a.source = nullptr;
   a.tab = aff_striped(a.tab);
   uint32_t dst = a.dst[i], dport = a.dport[i];
   uint32_t out_port = a.out_port[i];
   uint32_t svc_group = a.svc_group ? a.svc_group[i] : 0u;
   uint32_t dest = a.dest ? a.dest[i] : 0u;
+  const uint32_t source = a.source ? uint32_t(a.source[i]) : uint32_t(GPC_SOURCE_UNKNOWN);
   uint32_t lb[4];
   const uint32_t f = lb_stage_aff(a.svc, a.tab, a.now, a.seq, a.read_only != 0u, uint32_t(i), a.src[i], dst, a.sport[i], a.sport,
-                                  dport, a.proto[i], svc_group, out_port, dest, lb);
+                                  dport, a.proto[i], svc_group, out_port, dest, lb, source, a.source);
   if (!a.read_only) {
     AffOpsDev::count(a.tab.ctr + kAffLearned, (f & GPC_LB_LEARNED) != 0u);
     AffOpsDev::count(a.tab.ctr + kAffHits, (f & (GPC_LB_AFFINITY | GPC_LB_LEARNED)) == GPC_LB_AFFINITY);
@@ -1251,6 +1282,7 @@ int launch_classify_aff(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, 
   a.svc_group = pk.svc_group;
   a.dest = pk.dest;
   a.ct_state = pk.ct_state;
+  a.source = pk.source;
   a.dst_out = reinterpret_cast<uint32_t*>(take(4 * n));
   a.out_port_out = reinterpret_cast<uint32_t*>(take(4 * n));
   a.svc_group_out = reinterpret_cast<uint32_t*>(take(4 * n));
@@ -1260,10 +1292,12 @@ int launch_classify_aff(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, 
   const dim3 grid(uint32_t((n + kLbBlock - 1) / kLbBlock));
   if (!al.read_only) {
     launch_mark(marks, kLaunchAffLearn, stream);
-    hipLaunchKernelGGL(aff_learn_kernel, grid, dim3(kLbBlock), 0, stream, a, n);
+    if (a.source) hipLaunchKernelGGL(aff_learn_kernel<true>, grid, dim3(kLbBlock), 0, stream, a, n);
+    else hipLaunchKernelGGL(aff_learn_kernel<false>, grid, dim3(kLbBlock), 0, stream, a, n);
   }
   launch_mark(marks, kLaunchAffResolve, stream);
-  hipLaunchKernelGGL(aff_resolve_kernel, grid, dim3(kLbBlock), 0, stream, a, n);
+  if (a.source) hipLaunchKernelGGL(aff_resolve_kernel<true>, grid, dim3(kLbBlock), 0, stream, a, n);
+  else hipLaunchKernelGGL(aff_resolve_kernel<false>, grid, dim3(kLbBlock), 0, stream, a, n);
   // the table is free for the next affinity batch of the slot from here on
   if (al.done && hipEventRecord(al.done, stream) != hipSuccess) return -GPC_EDEV;
   gpc_pkt_soa p4 = pk;  // the policy launches read what the stage rewrote
@@ -1272,6 +1306,7 @@ int launch_classify_aff(const EpochArgs& ep, const gpc_pkt_soa& pk, uint64_t n, 
   p4.out_port = a.out_port_out;
   p4.svc_group = a.svc_group_out;
   p4.dest = a.dest_out;
+  p4.source = nullptr;  // read by the Service stage alone
   if (!p4.ct_dst) p4.ct_dst = pk.dst;  // ct_nw_dst: the destination before the DNAT
   if (rewritten) *rewritten = p4;
   if (!out) return hipGetLastError() == hipSuccess ? 0 : -GPC_EDEV;  // (gpc_trace: the Service stage alone)
@@ -1307,15 +1342,19 @@ __global__ __launch_bounds__(kLbBlock) void aff6_sweep_kernel(Aff6Table t, uint3
   const uint64_t s = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
   if (s < (uint64_t(1) << t.log2)) aff6_sweep_slot<AffOpsDev>(t, uint32_t(s), now, mode);
 }
+template <bool kSrc>
 __global__ __launch_bounds__(kLbBlock) void aff6_learn_kernel(Aff6Args a, uint64_t n) {
   const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
   if (i >= n) return;
+  if (!kSrc) a.pk.source = nullptr;
   a.tab = aff6_striped(a.tab);
   aff6_learn<AffOpsDev>(a.svc, a.tab, a.now, a.seq, uint32_t(i), a.pk);
 }
+template <bool kSrc>
 __global__ __launch_bounds__(kLbBlock) void aff6_resolve_kernel(Aff6Args a, uint64_t n) {
   const uint64_t i = uint64_t(blockIdx.x) * kLbBlock + threadIdx.x;
   if (i >= n) return;
+  if (!kSrc) a.pk.source = nullptr;
   a.tab = aff6_striped(a.tab);
   uint32_t dst[4];
   aff6_addr(a.pk.dst6, i, dst);
@@ -1347,7 +1386,7 @@ static int launch_aff6(const V6LbArgs& v, const gpc_pkt_soa& pk, uint64_t n, con
   a.tab = al.tab;
   a.now = al.now;
   a.seq = al.seq;
-  a.pk = Aff6Cols{pk.src6, pk.dst6, pk.sport, pk.dport, pk.proto, pk.ct_state, n};
+  a.pk = Aff6Cols{pk.src6, pk.dst6, pk.sport, pk.dport, pk.proto, pk.ct_state, n, v.source};
   a.out_port = v.out_port;
   a.svc_group = v.svc_group;
   a.dest = v.dest;
@@ -1359,9 +1398,11 @@ static int launch_aff6(const V6LbArgs& v, const gpc_pkt_soa& pk, uint64_t n, con
   a.lb_out = v.lb_out;
   const dim3 grid(uint32_t((n + kLbBlock - 1) / kLbBlock));
   launch_mark(marks, kLaunchAff6Learn, stream);
-  hipLaunchKernelGGL(aff6_learn_kernel, grid, dim3(kLbBlock), 0, stream, a, n);
+  if (a.pk.source) hipLaunchKernelGGL(aff6_learn_kernel<true>, grid, dim3(kLbBlock), 0, stream, a, n);
+  else hipLaunchKernelGGL(aff6_learn_kernel<false>, grid, dim3(kLbBlock), 0, stream, a, n);
   launch_mark(marks, kLaunchAff6Resolve, stream);
-  hipLaunchKernelGGL(aff6_resolve_kernel, grid, dim3(kLbBlock), 0, stream, a, n);
+  if (a.pk.source) hipLaunchKernelGGL(aff6_resolve_kernel<true>, grid, dim3(kLbBlock), 0, stream, a, n);
+  else hipLaunchKernelGGL(aff6_resolve_kernel<false>, grid, dim3(kLbBlock), 0, stream, a, n);
   // the table is free for the next affinity batch of the slot from here on
   if (al.done && hipEventRecord(al.done, stream) != hipSuccess) return -GPC_EDEV;
   return hipGetLastError() == hipSuccess ? 0 : -GPC_EDEV;

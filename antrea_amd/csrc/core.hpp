@@ -2165,6 +2165,9 @@ struct SvcHdr {
   // Session affinity (0 / 0 without an affinity Service): n_svc install ids (0: the Service has no
   // affinity), then n_np NodePort address ids, at aff_off
   uint32_t aff_off, n_aff;
+  // Short-circuit Services (external, externalTrafficPolicy: Local; gpc_config.packet_source): how
+  // many records carry kSvcShortCircuit (0: the batches' source column is never loaded)
+  uint32_t n_sc;
 };
 constexpr uint32_t kSvcMaxNodePortAddrs = 64;
 // Service hash: 2-choice cuckoo, buckets of two 16-B slots {key low, key high, service index, 0}:
@@ -2172,6 +2175,16 @@ constexpr uint32_t kSvcMaxNodePortAddrs = 64;
 constexpr uint32_t kSvcBucketWords = 8, kSvcSlots = 2, kSvcSlotWords = 4;
 constexpr uint32_t kSvcLoadReg7 = 1u;  // service flag: the ServiceLB flow loads reg7 = group id
 constexpr uint32_t kSvcAffinity = 2u;  // ... loads EpToLearnRegMark: session affinity, hard timeout in flags >> 16
+// ... has a short-circuit flow (serviceLBFlows priority 210, FromLocalRegMark): this record is the
+// TrafficPolicy (Local) group's, the record directly behind it the Cluster group's -- the one a packet
+// from a local Pod or the gateway takes (same reg7 / affinity flags, same install id at aff_off)
+constexpr uint32_t kSvcShortCircuit = 4u;
+// FromLocalRegMark (pipeline.go:540, 557): PktSourceField is gateway or Pod
+GPC_HD bool source_is_local(uint32_t source) { return source == GPC_SOURCE_GATEWAY || source == GPC_SOURCE_POD; }
+// Records to step from a Service's first record for a packet of that source (0 or 1).
+GPC_HD uint32_t svc_step(uint32_t rec_flags, uint32_t source) {
+  return (rec_flags & kSvcShortCircuit) && source_is_local(source) ? 1u : 0u;
+}
 // endpoint flags (port word >> 16): GPC_LB_DNAT / GPC_LB_REMOTE values
 GPC_HD uint64_t svc_key(uint32_t proto, uint32_t ip, uint32_t port) {
   return (1ull << 63) | (uint64_t(proto & 0xffu) << 48) | (uint64_t(port & 0xffffu) << 32) | ip;
@@ -2218,8 +2231,10 @@ GPC_HD uint32_t svc_lookup(const uint32_t* sv, uint32_t proto, uint32_t ip, uint
 // words {endpoint ip, port | flags << 16, group id, out_port}. Returns the GPC_LB_* flags (0: the
 // packet is not addressed to a Service). ct_nw_dst keeps the pre-NAT destination: the caller
 // takes it before this call.
+// `source`: the packet's gpc_source -- at a short-circuit Service a local one takes the Cluster
+// group's record (GPC_LB_SHORT_CIRCUIT), every other the Local group's.
 GPC_HD uint32_t lb_stage(const uint32_t* sv, uint32_t src, uint32_t& dst, uint32_t sport, uint32_t& dport, uint32_t proto,
-                         uint32_t& svc_group, uint32_t& out_port, uint32_t& dest, uint32_t* o) {
+                         uint32_t& svc_group, uint32_t& out_port, uint32_t& dest, uint32_t* o, uint32_t source) {
   o[0] = o[1] = o[2] = o[3] = 0;
   if (proto != 6 && proto != 17 && proto != 132) return 0;
   const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
@@ -2232,17 +2247,26 @@ GPC_HD uint32_t lb_stage(const uint32_t* sv, uint32_t src, uint32_t& dst, uint32
   if (si == 0xffffffffu) return 0;
   const uint32_t* s = sv + h->svc_off + 4 * si;
   GPC_TOUCH(s, 16);
-  const uint32_t n = s[1] & 0xffffffu, lg = s[1] >> 24;
   uint32_t flags = GPC_LB_HIT;
-  o[2] = s[2];
-  if (s[3] & kSvcLoadReg7) svc_group = s[2];
+  // The record's words are taken from the first record and replaced inside the branch: nothing a
+  // packet of another Service reads depends on the flags word (a stepped pointer would put every
+  // packet's record loads behind it, a dependent round of their own).
+  uint32_t r0 = s[0], r1 = s[1], r2 = s[2], r3 = s[3];
+  if (svc_step(r3, source)) {
+    GPC_TOUCH(s + 4, 16);
+    r0 = s[4], r1 = s[5], r2 = s[6], r3 = s[7];
+    flags |= GPC_LB_SHORT_CIRCUIT;
+  }
+  const uint32_t n = r1 & 0xffffffu, lg = r1 >> 24;
+  o[2] = r2;
+  if (r3 & kSvcLoadReg7) svc_group = r2;
   if (n == 0) {
     flags |= GPC_LB_NO_ENDPOINT;
     o[1] = flags << 16;
     return flags;
   }
   const uint32_t slot = lb_hash(src, dst, sport, dport, proto) & ((1u << lg) - 1u);
-  const uint32_t* e = sv + h->ep_off + 4 * (s[0] + slot % n);
+  const uint32_t* e = sv + h->ep_off + 4 * (r0 + slot % n);
   GPC_TOUCH(e, 16);
   flags |= e[1] >> 16;
   o[0] = e[0];
@@ -2255,6 +2279,10 @@ GPC_HD uint32_t lb_stage(const uint32_t* sv, uint32_t src, uint32_t& dst, uint32
   out_port = e[2];
   dest = e[3];
   return flags;
+}
+GPC_HD uint32_t lb_stage(const uint32_t* sv, uint32_t src, uint32_t& dst, uint32_t sport, uint32_t& dport, uint32_t proto,
+                         uint32_t& svc_group, uint32_t& out_port, uint32_t& dest, uint32_t* o) {
+  return lb_stage(sv, src, dst, sport, dport, proto, svc_group, out_port, dest, o, GPC_SOURCE_UNKNOWN);
 }
 
 // ------------------------------------------------------------------------------ Affinity table
@@ -2368,13 +2396,14 @@ GPC_HD void aff_sweep_slot(const AffTable& t, uint32_t slot, uint32_t now, uint3
 // found no slot.
 template <class Ops>
 GPC_HD void aff_learn(const uint32_t* sv, const AffTable& t, uint32_t now, uint32_t seq, uint32_t i, uint32_t src, uint32_t dst,
-                      uint32_t dport, uint32_t proto, uint32_t ct_state) {
+                      uint32_t dport, uint32_t proto, uint32_t ct_state, uint32_t source) {
   bool overflow = false;
   if ((ct_state & GPC_CT_NEW) && (proto == 6 || proto == 17 || proto == 132)) {
     const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
     uint32_t np_id;
     const uint32_t si = aff_svc_lookup(sv, proto, dst, dport, np_id);
     const uint32_t* s = sv + h->svc_off + 4 * size_t(si == kAffNone ? 0u : si);
+    if (si != kAffNone) s += 4 * svc_step(s[3], source);  // the record its source selects (same install id)
     if (si != kAffNone && (s[3] & kSvcAffinity) && (s[1] & 0xffffffu)) {
       const uint64_t key = aff_key(sv[h->aff_off + si], np_id, src);
       uint32_t c[4];
@@ -2393,32 +2422,55 @@ GPC_HD void aff_learn(const uint32_t* sv, const AffTable& t, uint32_t now, uint3
   }
   Ops::count(t.ctr + kAffOverflow, overflow);
 }
+template <class Ops>
+GPC_HD void aff_learn(const uint32_t* sv, const AffTable& t, uint32_t now, uint32_t seq, uint32_t i, uint32_t src, uint32_t dst,
+                      uint32_t dport, uint32_t proto, uint32_t ct_state) {
+  aff_learn<Ops>(sv, t, now, seq, i, src, dst, dport, proto, ct_state, GPC_SOURCE_UNKNOWN);
+}
 
 // lb_stage with the affinity branch (the resolve pass): `sport_col` is the batch's sport column at
 // caller indexes (the winner's choice is lb_hash with its sport: the rest of the hash input is the
 // key's). read_only (gpc_trace): the bid word is ignored and nothing is written. Returns the
 // GPC_LB_* flags, GPC_LB_AFFINITY / GPC_LB_LEARNED included.
+// Packet source (`source`, `source_col`: the packet's gpc_source and the batch's column at caller
+// indexes, null: UNKNOWN): the key is the same whatever the source; everything else -- Endpoint list,
+// modulus, group, "the entry's Endpoint still belongs to the Service" -- is that of the record the
+// packet's own source selects. The winner of a bid chooses from ITS record; a later packet of the key
+// whose own record does not hold that Endpoint takes its own hash choice and learns nothing (one
+// entry write per key and batch). A packet in front of the winner takes its own hash choice as well,
+// even when the entry of before the batch was valid for its record (it can be, now that validity
+// depends on the source: the other class bid): the winner overwrites that entry in this same pass,
+// so no other lane may read it -- the one case in which a packet loses a valid learned Endpoint, for
+// one batch, and only when one client address sends from both source classes inside it.
 GPC_HD uint32_t lb_stage_aff(const uint32_t* sv, const AffTable& t, uint32_t now, uint32_t seq, bool read_only, uint32_t i,
                              uint32_t src, uint32_t& dst, uint32_t sport, const uint16_t* sport_col, uint32_t& dport,
-                             uint32_t proto, uint32_t& svc_group, uint32_t& out_port, uint32_t& dest, uint32_t* o) {
+                             uint32_t proto, uint32_t& svc_group, uint32_t& out_port, uint32_t& dest, uint32_t* o,
+                             uint32_t source, const uint8_t* source_col) {
   o[0] = o[1] = o[2] = o[3] = 0;
   if (proto != 6 && proto != 17 && proto != 132) return 0;
   const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
   uint32_t np_id;
   const uint32_t si = aff_svc_lookup(sv, proto, dst, dport, np_id);
   if (si == kAffNone) return 0;
-  const uint32_t* s = sv + h->svc_off + 4 * size_t(si);
-  const uint32_t n = s[1] & 0xffffffu, lg = s[1] >> 24;
+  const uint32_t* const s0 = sv + h->svc_off + 4 * size_t(si);  // the Service's first record
   uint32_t flags = GPC_LB_HIT;
-  o[2] = s[2];
-  if (s[3] & kSvcLoadReg7) svc_group = s[2];
+  const uint32_t* s = s0;  // (read through only where an entry or a winner of the other class is judged)
+  uint32_t r0 = s0[0], r1 = s0[1], r2 = s0[2], r3 = s0[3];
+  if (svc_step(r3, source)) {  // lb_stage: the words replaced in the branch
+    s += 4;
+    r0 = s[0], r1 = s[1], r2 = s[2], r3 = s[3];
+    flags |= GPC_LB_SHORT_CIRCUIT;
+  }
+  const uint32_t n = r1 & 0xffffffu, lg = r1 >> 24;
+  o[2] = r2;
+  if (r3 & kSvcLoadReg7) svc_group = r2;
   if (n == 0) {
     flags |= GPC_LB_NO_ENDPOINT;
     o[1] = flags << 16;
     return flags;
   }
   uint32_t index = kAffNone, pick_sport = sport, slot = kAffNone;
-  if (s[3] & kSvcAffinity) {
+  if (r3 & kSvcAffinity) {
     const uint64_t key = aff_key(sv[h->aff_off + si], np_id, src);
     uint32_t c[4];
     aff_candidates(key, t.log2, c);
@@ -2428,8 +2480,18 @@ GPC_HD uint32_t lb_stage_aff(const uint32_t* sv, const AffTable& t, uint32_t now
       if (!read_only && uint32_t(bid >> 32) == ~seq) {  // a bid of this launch: winner = its low half
         const uint32_t w = uint32_t(bid);
         if (w <= i) {
-          pick_sport = sport_col[w];
-          flags |= GPC_LB_AFFINITY | (w == i ? uint32_t(GPC_LB_LEARNED) : 0u);
+          // the winner's record (it differs from this packet's only at a short-circuit Service)
+          const uint32_t* sw = s0 + 4 * svc_step(s0[3], source_col ? uint32_t(source_col[w]) : uint32_t(GPC_SOURCE_UNKNOWN));
+          if (sw == s) {
+            pick_sport = sport_col[w];
+            flags |= GPC_LB_AFFINITY | (w == i ? uint32_t(GPC_LB_LEARNED) : 0u);
+          } else {  // (w != i) its choice from its record, when this packet's record holds that Endpoint too
+            const uint32_t wn = sw[1] & 0xffffffu, wlg = sw[1] >> 24;
+            const uint32_t wi = (lb_hash(src, dst, sport_col[w], dport, proto) & ((1u << wlg) - 1u)) % (wn ? wn : 1u);
+            const uint32_t* we = sv + h->ep_off + 4 * (size_t(sw[0]) + wi);
+            index = wn ? aff_find_endpoint(sv, s, we[0], we[1] & 0xffffu, wi) : kAffNone;
+            if (index != kAffNone) flags |= GPC_LB_AFFINITY;
+          }
         }
       } else if (aff_entry_valid(sv, s, aff_entry(t, slot), now, &index)) {
         flags |= GPC_LB_AFFINITY;
@@ -2439,12 +2501,12 @@ GPC_HD uint32_t lb_stage_aff(const uint32_t* sv, const AffTable& t, uint32_t now
     }
   }
   if (index == kAffNone) index = (lb_hash(src, dst, pick_sport, dport, proto) & ((1u << lg) - 1u)) % n;
-  const uint32_t* e = sv + h->ep_off + 4 * (size_t(s[0]) + index);
+  const uint32_t* e = sv + h->ep_off + 4 * (size_t(r0) + index);
   if (flags & GPC_LB_LEARNED) {  // the winner: no other lane reads or writes this entry in this pass
     uint32_t* w = aff_entry(t, slot);
     w[0] = e[0];
     w[1] = (e[1] & 0xffffu) | (((e[1] >> 16) & GPC_LB_REMOTE) << 16);
-    w[2] = now + (s[3] >> 16);
+    w[2] = now + (r3 >> 16);
     w[3] = index;
   }
   flags |= e[1] >> 16;
@@ -2458,6 +2520,12 @@ GPC_HD uint32_t lb_stage_aff(const uint32_t* sv, const AffTable& t, uint32_t now
   out_port = e[2];
   dest = e[3];
   return flags;
+}
+GPC_HD uint32_t lb_stage_aff(const uint32_t* sv, const AffTable& t, uint32_t now, uint32_t seq, bool read_only, uint32_t i,
+                             uint32_t src, uint32_t& dst, uint32_t sport, const uint16_t* sport_col, uint32_t& dport,
+                             uint32_t proto, uint32_t& svc_group, uint32_t& out_port, uint32_t& dest, uint32_t* o) {
+  return lb_stage_aff(sv, t, now, seq, read_only, i, src, dst, sport, sport_col, dport, proto, svc_group, out_port, dest, o,
+                      GPC_SOURCE_UNKNOWN, nullptr);
 }
 
 // ------------------------------------------------------------------------- IPv6 Service image
@@ -2523,7 +2591,7 @@ GPC_HD uint32_t svc6_lookup(const uint32_t* sv, uint32_t proto, const uint32_t* 
 // lb_hash over the folded addresses -- the IPv4 bucket under a /96 embedding of both addresses.
 template <class SrcFn>
 GPC_HD uint32_t lb_stage6(const uint32_t* sv, SrcFn src, uint32_t* dst, uint32_t& dport, uint32_t proto, uint32_t& svc_group,
-                          uint32_t& out_port, uint32_t& dest, uint32_t* o) {
+                          uint32_t& out_port, uint32_t& dest, uint32_t* o, uint32_t source) {
   for (int k = 0; k < 8; k++) o[k] = 0;
   if (proto != 6 && proto != 17 && proto != 132) return 0;
   const SvcHdr* h = reinterpret_cast<const SvcHdr*>(sv);
@@ -2540,10 +2608,16 @@ GPC_HD uint32_t lb_stage6(const uint32_t* sv, SrcFn src, uint32_t* dst, uint32_t
   if (si == 0xffffffffu) return 0;
   const uint32_t* s = sv + h->svc_off + 4 * si;
   GPC_TOUCH(s, 16);
-  const uint32_t n = s[1] & 0xffffffu, lg = s[1] >> 24;
   uint32_t flags = GPC_LB_HIT;
-  o[5] = s[2];
-  if (s[3] & kSvcLoadReg7) svc_group = s[2];
+  uint32_t r0 = s[0], r1 = s[1], r2 = s[2], r3 = s[3];
+  if (svc_step(r3, source)) {  // lb_stage: the words replaced in the branch, no stepped pointer
+    GPC_TOUCH(s + 4, 16);
+    r0 = s[4], r1 = s[5], r2 = s[6], r3 = s[7];
+    flags |= GPC_LB_SHORT_CIRCUIT;
+  }
+  const uint32_t n = r1 & 0xffffffu, lg = r1 >> 24;
+  o[5] = r2;
+  if (r3 & kSvcLoadReg7) svc_group = r2;
   if (n == 0) {
     flags |= GPC_LB_NO_ENDPOINT;
     o[4] = flags << 16;
@@ -2551,7 +2625,7 @@ GPC_HD uint32_t lb_stage6(const uint32_t* sv, SrcFn src, uint32_t* dst, uint32_t
   }
   const Svc6Src sp = src();
   const uint32_t slot = lb_hash(sp.x, fold6(dst), sp.y, dport, proto) & ((1u << lg) - 1u);
-  const uint32_t* e = sv + h->ep_off + kSvc6EpWords * (s[0] + slot % n);
+  const uint32_t* e = sv + h->ep_off + kSvc6EpWords * (r0 + slot % n);
   GPC_TOUCH(e, 4 * kSvc6EpWords);
   flags |= e[4] >> 16;
   o[0] = e[0], o[1] = e[1], o[2] = e[2], o[3] = e[3];
@@ -2564,6 +2638,11 @@ GPC_HD uint32_t lb_stage6(const uint32_t* sv, SrcFn src, uint32_t* dst, uint32_t
   out_port = e[5];
   dest = e[6];
   return flags;
+}
+template <class SrcFn>
+GPC_HD uint32_t lb_stage6(const uint32_t* sv, SrcFn src, uint32_t* dst, uint32_t& dport, uint32_t proto, uint32_t& svc_group,
+                          uint32_t& out_port, uint32_t& dest, uint32_t* o) {
+  return lb_stage6(sv, src, dst, dport, proto, svc_group, out_port, dest, o, GPC_SOURCE_UNKNOWN);
 }
 
 // ------------------------------------------------------------------------- IPv6 affinity table
@@ -2601,7 +2680,9 @@ struct Aff6Cols {
   const uint16_t *sport, *dport;
   const uint8_t *proto, *ct_state;  // ct_state: optional
   uint64_t n;                       // packets of the batch
+  const uint8_t* source;            // gpc_source, optional (UNKNOWN): set only against an image with short-circuit Services
 };
+GPC_HD uint32_t aff6_source(const Aff6Cols& pk, uint64_t i) { return pk.source ? uint32_t(pk.source[i]) : uint32_t(GPC_SOURCE_UNKNOWN); }
 GPC_HD void aff6_addr(const uint8_t* col, uint64_t i, uint32_t* a) {  // one 128-bit load
 #if defined(__HIPCC__)
   const uint4 v = reinterpret_cast<const uint4*>(col)[i];
@@ -2686,6 +2767,7 @@ GPC_HD void aff6_learn(const uint32_t* sv, const Aff6Table& t, uint32_t now, uin
     aff6_addr(pk.dst6, i, dst);
     const uint32_t si = aff6_svc_lookup(sv, proto, dst, pk.dport[i], np_id);
     const uint32_t* s = sv + h->svc_off + 4 * size_t(si == kAffNone ? 0u : si);
+    if (si != kAffNone) s += 4 * svc_step(s[3], aff6_source(pk, i));  // the record its source selects (same install id)
     if (si != kAffNone && (s[3] & kSvcAffinity) && (s[1] & 0xffffffu)) {
       uint32_t src[4], c[4];
       aff6_addr(pk.src6, i, src);
@@ -2727,11 +2809,18 @@ GPC_HD uint32_t lb_stage6_aff(const uint32_t* sv, const Aff6Table& t, uint32_t n
   uint32_t np_id;
   const uint32_t si = aff6_svc_lookup(sv, proto, dst, dport, np_id);
   if (si == kAffNone) return 0;
-  const uint32_t* s = sv + h->svc_off + 4 * size_t(si);
-  const uint32_t n = s[1] & 0xffffffu, lg = s[1] >> 24;
+  const uint32_t* const s0 = sv + h->svc_off + 4 * size_t(si);  // the Service's first record
   uint32_t flags = GPC_LB_HIT;
-  o[5] = s[2];
-  if (s[3] & kSvcLoadReg7) svc_group = s[2];
+  const uint32_t* s = s0;
+  uint32_t r0 = s0[0], r1 = s0[1], r2 = s0[2], r3 = s0[3];
+  if (svc_step(r3, aff6_source(pk, i))) {  // lb_stage_aff: the record the packet's source selects
+    s += 4;
+    r0 = s[0], r1 = s[1], r2 = s[2], r3 = s[3];
+    flags |= GPC_LB_SHORT_CIRCUIT;
+  }
+  const uint32_t n = r1 & 0xffffffu, lg = r1 >> 24;
+  o[5] = r2;
+  if (r3 & kSvcLoadReg7) svc_group = r2;
   if (n == 0) {
     flags |= GPC_LB_NO_ENDPOINT;
     o[4] = flags << 16;
@@ -2740,7 +2829,7 @@ GPC_HD uint32_t lb_stage6_aff(const uint32_t* sv, const Aff6Table& t, uint32_t n
   uint32_t src[4];
   aff6_addr(pk.src6, i, src);
   uint32_t index = kAffNone, pick_sport = pk.sport[i], slot = kAffNone, id = 0;
-  if (s[3] & kSvcAffinity) {
+  if (r3 & kSvcAffinity) {
     id = (sv[h->aff_off + si] << 8) | (np_id & 0xffu);
     const uint64_t digest = aff6_digest(id, src, t.mask);
     uint32_t c[4];
@@ -2757,8 +2846,17 @@ GPC_HD uint32_t lb_stage6_aff(const uint32_t* sv, const Aff6Table& t, uint32_t n
         aff6_addr(pk.dst6, w, wd);
         if (aff6_same(ws, src) && aff6_same(wd, dst) && pk.dport[w] == dport && pk.proto[w] == proto) {
           if (w <= i) {
-            pick_sport = pk.sport[w];
-            flags |= GPC_LB_AFFINITY | (w == i ? uint32_t(GPC_LB_LEARNED) : 0u);
+            const uint32_t* sw = s0 + 4 * svc_step(s0[3], aff6_source(pk, w));  // the winner's record (lb_stage_aff)
+            if (sw == s) {
+              pick_sport = pk.sport[w];
+              flags |= GPC_LB_AFFINITY | (w == i ? uint32_t(GPC_LB_LEARNED) : 0u);
+            } else {  // (w != i) its choice from its record, when this packet's record holds that Endpoint too
+              const uint32_t wn = sw[1] & 0xffffffu, wlg = sw[1] >> 24;
+              const uint32_t wi = (lb_hash(fold6(src), fold6(dst), pk.sport[w], dport, proto) & ((1u << wlg) - 1u)) % (wn ? wn : 1u);
+              const uint32_t* we = sv + h->ep_off + kSvc6EpWords * (size_t(sw[0]) + wi);
+              index = wn ? aff6_find_endpoint(sv, s, we, we[4] & 0xffffu, wi) : kAffNone;
+              if (index != kAffNone) flags |= GPC_LB_AFFINITY;
+            }
           }
         } else {
           *collided = (ct_state & GPC_CT_NEW) != 0u;  // another key's digest won the slot in this pass
@@ -2776,13 +2874,13 @@ GPC_HD uint32_t lb_stage6_aff(const uint32_t* sv, const Aff6Table& t, uint32_t n
   }
   const uint32_t fdst = fold6(dst);  // the pre-NAT destination
   if (index == kAffNone) index = (lb_hash(fold6(src), fdst, pick_sport, dport, proto) & ((1u << lg) - 1u)) % n;
-  const uint32_t* e = sv + h->ep_off + kSvc6EpWords * (size_t(s[0]) + index);
+  const uint32_t* e = sv + h->ep_off + kSvc6EpWords * (size_t(r0) + index);
   if (!kReadOnly && (flags & GPC_LB_LEARNED)) {  // the winner: no other lane reads or writes these words in this pass
     uint32_t* b = aff6_body(t, slot);
     b[0] = src[0], b[1] = src[1], b[2] = src[2], b[3] = src[3];
     b[4] = e[0], b[5] = e[1], b[6] = e[2], b[7] = e[3];
     b[8] = (e[4] & 0xffffu) | (((e[4] >> 16) & GPC_LB_REMOTE) << 16);
-    b[9] = now + (s[3] >> 16);
+    b[9] = now + (r3 >> 16);
     b[10] = index;
     b[11] = id;
   }

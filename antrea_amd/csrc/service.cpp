@@ -27,6 +27,7 @@ constexpr uint32_t kToNodePort = 1u << 19;         // reg4[19]  ToNodePortAddres
 constexpr uint32_t kToExternal = 1u << 21;         // reg4[21]  ToExternalAddressRegMark
 constexpr uint32_t kVirtualNodePortDNAT = 0xa9fe00fcu;  // config.VirtualNodePortDNATIPv4 169.254.0.252
 constexpr uint32_t kRemoteEndpoint = 1u << 26;     // reg4[26]  RemoteEndpointRegMark
+constexpr uint32_t kFromLocal = 1u << 28;          // reg4[28]  FromLocalRegMark
 constexpr uint32_t kEpUnionMask = 0x7ffffu;        // reg4[0..18] EpUnionField
 // config.VirtualNodePortDNATIPv6 fc01::aabb:ccdd:eefe (node_config.go:84)
 constexpr uint8_t kVirtualNodePortDNAT6[16] = {0xfc, 0x01, 0, 0, 0, 0, 0, 0, 0, 0, 0xaa, 0xbb, 0xcc, 0xdd, 0xee, 0xfe};
@@ -225,8 +226,10 @@ static std::string service_key(const IPAddr& ip, uint16_t port, uint8_t proto) {
 // InstallServiceFlows (client.go:790-807) -> serviceLBFlows (pipeline.go:2373-2431).
 int FeatureService::install_service_flows(const gpc_service_config& c) {
   if (!ip_proto(c.protocol) || !family_ok(c.family)) return -GPC_EINVAL;
-  if (c.is_dsr || c.is_nested || (c.is_external && c.traffic_policy_local))
-    return -GPC_EINVAL;  // DSR / multi-cluster / short-circuit flows: not modelled
+  if (c.is_dsr || c.is_nested) return -GPC_EINVAL;  // DSR / multi-cluster flows: not modelled
+  // the short-circuit flow matches FromLocalRegMark: only batches of a packet_source context can tell
+  const bool short_circuit = c.is_external && c.traffic_policy_local;
+  if (short_circuit && !cfg_.packet_source) return -GPC_EINVAL;
   // learn flows: Services of a context with an affinity table for their family
   if (c.affinity_timeout && !(c.family == 6 ? cfg_.session_affinity6 : cfg_.session_affinity)) return -GPC_EINVAL;
   if (c.affinity_timeout && next_install_ >= kMaxInstallId) return -GPC_ENOMEM;
@@ -254,7 +257,18 @@ int FeatureService::install_service_flows(const gpc_service_config& c) {
   Action g{ACT_GROUP};
   g.a = gid;
   f.acts.push_back(g);
-  std::vector<Flow> flows = {f};
+  std::vector<Flow> flows;
+  if (short_circuit) {  // pipeline.go:2417-2422: from a local Pod or the Node -> the Cluster group
+    Flow sc = f;
+    sc.priority = kPriorityHigh;
+    match_reg(sc.m, 4, kFromLocal, kFromLocal);
+    for (auto& a : sc.acts) {
+      if (a.kind == ACT_SET_REG && a.a == 7) a.b = c.cluster_group_id;
+      if (a.kind == ACT_GROUP) a.a = c.cluster_group_id;
+    }
+    flows.push_back(sc);
+  }
+  flows.push_back(f);
   if (c.affinity_timeout) {  // serviceLearnFlow (pipeline.go:2316-2371)
     Flow l;
     l.table = TB_SERVICE_LB;
@@ -481,6 +495,29 @@ static bool group_is_v4(const Group& g) {
   return false;
 }
 
+// Pairs every priority-210 ServiceLB flow (`short_circuit`, per Service key) with the priority-200 flow
+// of its key in `svcs`: that Service gets sc / sc_gid. A short-circuit flow without its priority-200
+// flow, or one whose loads (reg7, EpToLearn) differ from it, is a shape the data path does not implement.
+template <class Svc, class Map, class KeyFn>
+static int pair_short_circuit(std::vector<Svc>& svcs, Map& short_circuit, KeyFn key_of, std::string* err) {
+  for (auto& s : svcs) {
+    const auto it = short_circuit.find(key_of(s));
+    if (it == short_circuit.end()) continue;
+    if (it->second.reg7 != s.reg7 || it->second.aff != s.aff) {
+      *err = "ServiceLB short-circuit flow whose loads differ from its priority-200 flow (group " + std::to_string(s.gid) + ")";
+      return -GPC_EINVAL;
+    }
+    s.sc = true;
+    s.sc_gid = it->second.gid;
+    short_circuit.erase(it);
+  }
+  if (!short_circuit.empty()) {
+    *err = "ServiceLB short-circuit flow without its priority-200 flow (group " + std::to_string(short_circuit.begin()->second.gid) + ")";
+    return -GPC_EINVAL;
+  }
+  return GPC_OK;
+}
+
 bool FeatureService::has_state(uint8_t family) const {
   for (auto& kv : cached_)
     for (auto& f : kv.second)
@@ -504,12 +541,15 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
     uint32_t gid;
     bool reg7;
     bool aff;  // the ServiceLB flow loads EpToLearnRegMark: its learn flow follows the group
+    bool sc = false;      // a short-circuit flow (priority 210, FromLocalRegMark) exists beside it ...
+    uint32_t sc_gid = 0;  // ... to this (Cluster) group
   };
   struct Learn {
     uint32_t timeout, install;
   };
   std::map<uint64_t, Learn> learn;  // serviceLearnFlow per Service key
   std::vector<Svc> svcs;
+  std::map<uint64_t, Svc> short_circuit;  // the priority-210 flows per Service key
   std::vector<uint32_t> node_port_addrs;
   bool any_node_port = false;
   for (auto& kv : cached_)
@@ -533,6 +573,7 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
         const bool node_port = (f.m.reg_present & (1u << 4)) && (f.m.reg_m[4] & kToNodePort) && (f.m.reg_v[4] & kToNodePort);
         any_node_port |= node_port;
         Svc s{svc_key(f.m.nw_proto, node_port ? 0u : f.m.nw_dst.addr.v4(), f.m.tp_dst), 0, false, false};
+        const bool from_local = (f.m.reg_present & (1u << 4)) && (f.m.reg_m[4] & kFromLocal) && (f.m.reg_v[4] & kFromLocal);
         if (!f.acts.empty() && f.acts[0].kind == ACT_LEARN) {  // learn(...), EpSelected, goto EndpointDNAT
           const Action& l = f.acts[0];
           if ((f.m.reg_v[4] & kEpStateMask) != kEpToLearn || node_port == f.m.nw_dst.set || !f.m.has_tp_dst ||
@@ -555,11 +596,20 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
           *err = "unsupported ServiceLB flow: " + f.str();
           return -GPC_EINVAL;
         }
+        if (from_local) {  // the short-circuit flow of the priority-200 flow with the same key
+          if (f.priority != kPriorityHigh || short_circuit.count(s.key)) {
+            *err = "unsupported ServiceLB short-circuit flow: " + f.str();
+            return -GPC_EINVAL;
+          }
+          short_circuit[s.key] = s;
+          continue;
+        }
         svcs.push_back(s);
       }
     }
+  if (const int rc = pair_short_circuit(svcs, short_circuit, [](const Svc& x) { return x.key; }, err)) return rc;
   std::vector<uint32_t> svc_words, ep_words, aff_ids;
-  uint32_t n_aff = 0;
+  uint32_t n_aff = 0, n_sc = 0;
   std::vector<std::pair<uint64_t, uint32_t>> kv;
   for (auto& s : svcs) {
     const auto lit = learn.find(s.key);
@@ -567,59 +617,65 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
       *err = "ServiceLB flow loads EpToLearnRegMark without a learn flow (group " + std::to_string(s.gid) + ")";
       return -GPC_EINVAL;
     }
-    uint32_t first = uint32_t(ep_words.size() / 4), n = 0;
-    auto git = groups_.find(s.gid);
-    if (git != groups_.end() && group_is_v6(git->second)) {
-      *err = "IPv4 Service with an IPv6 Endpoint group: " + git->second.str();
-      return -GPC_EINVAL;
-    }
-    if (git != groups_.end()) {
-      for (auto& b : git->second.buckets) {
-        uint32_t ip = 0, port = 0, flags = 0;
-        bool noep = false, to_dnat = false, to_lb = false;
-        for (auto& a : b.acts) {
-          if (a.kind == ACT_SET_REG && a.a == 3) ip = a.b;
-          if (a.kind == ACT_SET_REG && a.a == 4 && a.c == 0xffffu) port = a.b;
-          if (a.kind == ACT_SET_REG && a.a == 4 && (a.b & kRemoteEndpoint)) flags |= GPC_LB_REMOTE;
-          if (a.kind == ACT_SET_REG && a.a == 0 && (a.b & kSvcNoEp)) noep = true;
-          if (a.kind == ACT_RESUBMIT) to_dnat = a.a == TB_ENDPOINT_DNAT, to_lb = a.a == TB_SERVICE_LB;
-        }
-        // a session-affinity bucket resubmits to ServiceLB, where the Service's learn flow takes the
-        // packet on to EndpointDNAT: bucket -> learn flow -> EndpointDNAT
-        if (!(to_dnat || (to_lb && s.aff)) || (to_lb && noep)) {
-          *err = "unsupported group bucket (session affinity): " + git->second.str();
-          return -GPC_EINVAL;
-        }
-        if (s.aff && to_dnat && !noep) {
-          *err = "session-affinity Service whose group bypasses its learn flow: " + git->second.str();
-          return -GPC_EINVAL;
-        }
-        if (noep) continue;
-        auto d = dnat.find({uint8_t((s.key >> 48) & 0xff), ip, uint16_t(port)});
-        if (d != dnat.end()) flags |= GPC_LB_DNAT;
-        uint32_t out_port = 0, dest = GPC_DEST_GATEWAY;
-        auto pit = pods_.find(ip);
-        if (pit != pods_.end()) {
-          out_port = pit->second;
-          dest = GPC_DEST_POD;
-        } else if (flags & GPC_LB_REMOTE) {
-          dest = GPC_DEST_TUNNEL;
-        }
-        ep_words.insert(ep_words.end(), {ip, port | (flags << 16), out_port, dest});
-        n++;
+    // a short-circuit Service: its Local group's record, then its Cluster group's directly behind
+    for (uint32_t r = 0; r < (s.sc ? 2u : 1u); r++) {
+      const uint32_t gid = r ? s.sc_gid : s.gid;
+      uint32_t first = uint32_t(ep_words.size() / 4), n = 0;
+      auto git = groups_.find(gid);
+      if (git != groups_.end() && group_is_v6(git->second)) {
+        *err = "IPv4 Service with an IPv6 Endpoint group: " + git->second.str();
+        return -GPC_EINVAL;
       }
+      if (git != groups_.end()) {
+        for (auto& b : git->second.buckets) {
+          uint32_t ip = 0, port = 0, flags = 0;
+          bool noep = false, to_dnat = false, to_lb = false;
+          for (auto& a : b.acts) {
+            if (a.kind == ACT_SET_REG && a.a == 3) ip = a.b;
+            if (a.kind == ACT_SET_REG && a.a == 4 && a.c == 0xffffu) port = a.b;
+            if (a.kind == ACT_SET_REG && a.a == 4 && (a.b & kRemoteEndpoint)) flags |= GPC_LB_REMOTE;
+            if (a.kind == ACT_SET_REG && a.a == 0 && (a.b & kSvcNoEp)) noep = true;
+            if (a.kind == ACT_RESUBMIT) to_dnat = a.a == TB_ENDPOINT_DNAT, to_lb = a.a == TB_SERVICE_LB;
+          }
+          // a session-affinity bucket resubmits to ServiceLB, where the Service's learn flow takes the
+          // packet on to EndpointDNAT: bucket -> learn flow -> EndpointDNAT
+          if (!(to_dnat || (to_lb && s.aff)) || (to_lb && noep)) {
+            *err = "unsupported group bucket (session affinity): " + git->second.str();
+            return -GPC_EINVAL;
+          }
+          if (s.aff && to_dnat && !noep) {
+            *err = "session-affinity Service whose group bypasses its learn flow: " + git->second.str();
+            return -GPC_EINVAL;
+          }
+          if (noep) continue;
+          auto d = dnat.find({uint8_t((s.key >> 48) & 0xff), ip, uint16_t(port)});
+          if (d != dnat.end()) flags |= GPC_LB_DNAT;
+          uint32_t out_port = 0, dest = GPC_DEST_GATEWAY;
+          auto pit = pods_.find(ip);
+          if (pit != pods_.end()) {
+            out_port = pit->second;
+            dest = GPC_DEST_POD;
+          } else if (flags & GPC_LB_REMOTE) {
+            dest = GPC_DEST_TUNNEL;
+          }
+          ep_words.insert(ep_words.end(), {ip, port | (flags << 16), out_port, dest});
+          n++;
+        }
+      }
+      uint32_t lg = 6;
+      while ((1u << lg) < n) lg++;
+      if (n >= (1u << 24)) {
+        *err = "too many Endpoints in one group";
+        return -GPC_EINVAL;
+      }
+      if (r == 0) kv.push_back({s.key, uint32_t(svc_words.size() / 4)});
+      svc_words.insert(svc_words.end(), {first, n | (lg << 24), gid,
+                                         (s.reg7 ? kSvcLoadReg7 : 0u) | (s.aff ? kSvcAffinity | (lit->second.timeout << 16) : 0u) |
+                                             (s.sc && r == 0 ? kSvcShortCircuit : 0u)});
+      aff_ids.push_back(s.aff ? lit->second.install : 0u);
     }
-    uint32_t lg = 6;
-    while ((1u << lg) < n) lg++;
-    if (n >= (1u << 24)) {
-      *err = "too many Endpoints in one group";
-      return -GPC_EINVAL;
-    }
-    kv.push_back({s.key, uint32_t(svc_words.size() / 4)});
-    svc_words.insert(svc_words.end(), {first, n | (lg << 24), s.gid,
-                                       (s.reg7 ? kSvcLoadReg7 : 0u) | (s.aff ? kSvcAffinity | (lit->second.timeout << 16) : 0u)});
-    aff_ids.push_back(s.aff ? lit->second.install : 0u);
     n_aff += s.aff;
+    n_sc += s.sc;
   }
   SvcHash h;
   if (!h.build(kv)) {
@@ -648,6 +704,7 @@ int FeatureService::build_image(std::vector<uint32_t>* blob, std::string* err) c
   // session affinity: the install id of every Service (0: none) and the id of every NodePort
   // address, after the rest -- an image without an affinity Service has neither
   hdr.n_aff = n_aff;
+  hdr.n_sc = n_sc;
   hdr.aff_off = n_aff ? hdr.np_off + hdr.n_np : 0u;
   blob->assign(hdr.np_off + node_port_addrs.size() + (n_aff ? aff_ids.size() + node_port_addrs.size() : 0), 0u);
   std::copy(node_port_addrs.begin(), node_port_addrs.end(), blob->begin() + hdr.np_off);
@@ -689,13 +746,17 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
     uint32_t gid;
     bool reg7;
     bool aff;  // the ServiceLB flow loads EpToLearnRegMark: its learn flow follows the group
+    bool sc = false;      // a short-circuit flow (priority 210, FromLocalRegMark) exists beside it ...
+    uint32_t sc_gid = 0;  // ... to this (Cluster) group
   };
   struct Learn {
     uint32_t timeout, install;
   };
   typedef std::tuple<uint8_t, uint16_t, std::array<uint32_t, 4>> SvcKey;  // (protocol, port, address; 0: NodePort)
   std::map<SvcKey, Learn> learn;  // serviceLearnFlow per Service key
+  std::map<SvcKey, Svc> short_circuit;  // the priority-210 flows per Service key
   std::vector<Svc> svcs;
+  std::vector<uint32_t> rec_svc;  // service record -> index into svcs
   std::vector<IPAddr> node_port_addrs;
   bool any_node_port = false;
   for (auto& kv : cached_)
@@ -719,6 +780,7 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
         any_node_port |= node_port;
         Svc s{f.m.nw_proto, f.m.tp_dst, {0, 0, 0, 0}, 0, false, false};
         if (!node_port && f.m.nw_dst.set) words_of(f.m.nw_dst.addr.b, s.a);
+        const bool from_local = (f.m.reg_present & (1u << 4)) && (f.m.reg_m[4] & kFromLocal) && (f.m.reg_v[4] & kFromLocal);
         if (!f.acts.empty() && f.acts[0].kind == ACT_LEARN) {  // learn(...), EpSelected, goto EndpointDNAT
           const Action& l = f.acts[0];
           if ((f.m.reg_v[4] & kEpStateMask) != kEpToLearn || node_port == f.m.nw_dst.set || !f.m.has_tp_dst ||
@@ -741,11 +803,22 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
           *err = "unsupported ServiceLB flow: " + f.str();
           return -GPC_EINVAL;
         }
+        if (from_local) {  // the short-circuit flow of the priority-200 flow with the same key (build_image)
+          const SvcKey key{s.proto, s.port, {s.a[0], s.a[1], s.a[2], s.a[3]}};
+          if (f.priority != kPriorityHigh || short_circuit.count(key)) {
+            *err = "unsupported ServiceLB short-circuit flow: " + f.str();
+            return -GPC_EINVAL;
+          }
+          short_circuit[key] = s;
+          continue;
+        }
         svcs.push_back(s);
       }
     }
+  if (const int rc = pair_short_circuit(svcs, short_circuit, [](const Svc& x) { return SvcKey{x.proto, x.port, {x.a[0], x.a[1], x.a[2], x.a[3]}}; }, err))
+    return rc;
   std::vector<uint32_t> svc_words, ep_words, aff_ids;
-  uint32_t n_aff = 0;
+  uint32_t n_aff = 0, n_sc = 0;
   std::vector<std::pair<uint64_t, uint32_t>> kv;
   for (auto& s : svcs) {
     const auto lit = learn.find(SvcKey{s.proto, s.port, {s.a[0], s.a[1], s.a[2], s.a[3]}});
@@ -753,66 +826,72 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
       *err = "ServiceLB flow loads EpToLearnRegMark without a learn flow (group " + std::to_string(s.gid) + ")";
       return -GPC_EINVAL;
     }
-    uint32_t first = uint32_t(ep_words.size() / kSvc6EpWords), n = 0;
-    auto git = groups_.find(s.gid);
-    if (git != groups_.end() && group_is_v4(git->second)) {
-      *err = "IPv6 Service with an IPv4 Endpoint group: " + git->second.str();
-      return -GPC_EINVAL;
-    }
-    if (git != groups_.end()) {
-      for (auto& b : git->second.buckets) {
-        IPAddr ip;
-        ip.fam = 6;
-        uint32_t port = 0, flags = 0;
-        bool noep = false, to_dnat = false, to_lb = false;
-        for (auto& a : b.acts) {
-          if (a.kind == ACT_SET_XXREG3)
-            for (int k = 0; k < 8; k++) {
-              ip.b[k] = uint8_t(a.lv >> (56 - 8 * k));
-              ip.b[8 + k] = uint8_t(a.lm >> (56 - 8 * k));
-            }
-          if (a.kind == ACT_SET_REG && a.a == 4 && a.c == 0xffffu) port = a.b;
-          if (a.kind == ACT_SET_REG && a.a == 4 && (a.b & kRemoteEndpoint)) flags |= GPC_LB_REMOTE;
-          if (a.kind == ACT_SET_REG && a.a == 0 && (a.b & kSvcNoEp)) noep = true;
-          if (a.kind == ACT_RESUBMIT) to_dnat = a.a == TB_ENDPOINT_DNAT, to_lb = a.a == TB_SERVICE_LB;
-        }
-        // a session-affinity bucket resubmits to ServiceLB, where the Service's learn flow takes the
-        // packet on to EndpointDNAT (build_image)
-        if (!(to_dnat || (to_lb && s.aff)) || (to_lb && noep)) {
-          *err = "unsupported group bucket (session affinity): " + git->second.str();
-          return -GPC_EINVAL;
-        }
-        if (s.aff && to_dnat && !noep) {
-          *err = "session-affinity Service whose group bypasses its learn flow: " + git->second.str();
-          return -GPC_EINVAL;
-        }
-        if (noep) continue;
-        if (dnat.count({s.proto, ip, uint16_t(port)})) flags |= GPC_LB_DNAT;
-        uint32_t out_port = 0, dest = GPC_DEST_GATEWAY;
-        auto pit = pods6_.find(ip);
-        if (pit != pods6_.end()) {
-          out_port = pit->second;
-          dest = GPC_DEST_POD;
-        } else if (flags & GPC_LB_REMOTE) {
-          dest = GPC_DEST_TUNNEL;
-        }
-        uint32_t w[4];
-        words_of(ip.b, w);
-        ep_words.insert(ep_words.end(), {w[0], w[1], w[2], w[3], port | (flags << 16), out_port, dest, 0u});
-        n++;
+    for (uint32_t r = 0; r < (s.sc ? 2u : 1u); r++) {  // build_image
+      const uint32_t gid = r ? s.sc_gid : s.gid;
+      uint32_t first = uint32_t(ep_words.size() / kSvc6EpWords), n = 0;
+      auto git = groups_.find(gid);
+      if (git != groups_.end() && group_is_v4(git->second)) {
+        *err = "IPv6 Service with an IPv4 Endpoint group: " + git->second.str();
+        return -GPC_EINVAL;
       }
+      if (git != groups_.end()) {
+        for (auto& b : git->second.buckets) {
+          IPAddr ip;
+          ip.fam = 6;
+          uint32_t port = 0, flags = 0;
+          bool noep = false, to_dnat = false, to_lb = false;
+          for (auto& a : b.acts) {
+            if (a.kind == ACT_SET_XXREG3)
+              for (int k = 0; k < 8; k++) {
+                ip.b[k] = uint8_t(a.lv >> (56 - 8 * k));
+                ip.b[8 + k] = uint8_t(a.lm >> (56 - 8 * k));
+              }
+            if (a.kind == ACT_SET_REG && a.a == 4 && a.c == 0xffffu) port = a.b;
+            if (a.kind == ACT_SET_REG && a.a == 4 && (a.b & kRemoteEndpoint)) flags |= GPC_LB_REMOTE;
+            if (a.kind == ACT_SET_REG && a.a == 0 && (a.b & kSvcNoEp)) noep = true;
+            if (a.kind == ACT_RESUBMIT) to_dnat = a.a == TB_ENDPOINT_DNAT, to_lb = a.a == TB_SERVICE_LB;
+          }
+          // a session-affinity bucket resubmits to ServiceLB, where the Service's learn flow takes the
+          // packet on to EndpointDNAT (build_image)
+          if (!(to_dnat || (to_lb && s.aff)) || (to_lb && noep)) {
+            *err = "unsupported group bucket (session affinity): " + git->second.str();
+            return -GPC_EINVAL;
+          }
+          if (s.aff && to_dnat && !noep) {
+            *err = "session-affinity Service whose group bypasses its learn flow: " + git->second.str();
+            return -GPC_EINVAL;
+          }
+          if (noep) continue;
+          if (dnat.count({s.proto, ip, uint16_t(port)})) flags |= GPC_LB_DNAT;
+          uint32_t out_port = 0, dest = GPC_DEST_GATEWAY;
+          auto pit = pods6_.find(ip);
+          if (pit != pods6_.end()) {
+            out_port = pit->second;
+            dest = GPC_DEST_POD;
+          } else if (flags & GPC_LB_REMOTE) {
+            dest = GPC_DEST_TUNNEL;
+          }
+          uint32_t w[4];
+          words_of(ip.b, w);
+          ep_words.insert(ep_words.end(), {w[0], w[1], w[2], w[3], port | (flags << 16), out_port, dest, 0u});
+          n++;
+        }
+      }
+      uint32_t lg = 6;
+      while ((1u << lg) < n) lg++;
+      if (n >= (1u << 24)) {
+        *err = "too many Endpoints in one group";
+        return -GPC_EINVAL;
+      }
+      if (r == 0) kv.push_back({svc6_hash_key(s.proto, s.a, s.port), uint32_t(svc_words.size() / 4)});
+      rec_svc.push_back(uint32_t(&s - svcs.data()));
+      svc_words.insert(svc_words.end(), {first, n | (lg << 24), gid,
+                                         (s.reg7 ? kSvcLoadReg7 : 0u) | (s.aff ? kSvcAffinity | (lit->second.timeout << 16) : 0u) |
+                                             (s.sc && r == 0 ? kSvcShortCircuit : 0u)});
+      aff_ids.push_back(s.aff ? lit->second.install : 0u);
     }
-    uint32_t lg = 6;
-    while ((1u << lg) < n) lg++;
-    if (n >= (1u << 24)) {
-      *err = "too many Endpoints in one group";
-      return -GPC_EINVAL;
-    }
-    kv.push_back({svc6_hash_key(s.proto, s.a, s.port), uint32_t(svc_words.size() / 4)});
-    svc_words.insert(svc_words.end(), {first, n | (lg << 24), s.gid,
-                                       (s.reg7 ? kSvcLoadReg7 : 0u) | (s.aff ? kSvcAffinity | (lit->second.timeout << 16) : 0u)});
-    aff_ids.push_back(s.aff ? lit->second.install : 0u);
     n_aff += s.aff;
+    n_sc += s.sc;
   }
   SvcHash h;
   if (!h.build(kv)) {
@@ -840,6 +919,7 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
   // session affinity: the install id of every Service (0: none) and the id of every NodePort
   // address, after the rest -- an image without an affinity Service has neither
   hdr.n_aff = n_aff;
+  hdr.n_sc = n_sc;
   hdr.aff_off = n_aff ? hdr.np_off + 4 * hdr.n_np : 0u;
   blob->assign(hdr.np_off + 4 * node_port_addrs.size() + (n_aff ? aff_ids.size() + node_port_addrs.size() : 0), 0u);
   for (size_t i = 0; i < node_port_addrs.size(); i++) words_of(node_port_addrs[i].b, blob->data() + hdr.np_off + 4 * i);
@@ -860,7 +940,7 @@ int FeatureService::build_image6(std::vector<uint32_t>* blob, std::string* err) 
     for (uint32_t i = 0; i < kSvcSlots; i++) {
       if (!h.keys[size_t(b) * kSvcSlots + i]) continue;  // an empty slot: tag word 0 never matches
       const uint32_t si = h.vals[size_t(b) * kSvcSlots + i];
-      const Svc& s = svcs[si];
+      const Svc& s = svcs[rec_svc[si]];
       uint32_t* slot = w + kSvc6SlotWords * i;
       for (int k = 0; k < 4; k++) slot[k] = s.a[k];
       slot[4] = svc6_tag(s.proto, s.port);

@@ -41,6 +41,9 @@ LB6_DTYPE = np.dtype([("endpoint_ip", "u1", (16,)), ("endpoint_port", "<u2"), ("
                       ("group_id", "<u4"), ("out_port", "<u4"), ("reserved2", "<u4")])
 LB_HIT, LB_NO_ENDPOINT, LB_DNAT, LB_REMOTE = 1, 2, 4, 8
 LB_AFFINITY, LB_LEARNED = 0x10, 0x20  # session affinity: Endpoint from a learned entry / this packet created it
+LB_SHORT_CIRCUIT = 0x40  # the priority-210 ServiceLB flow decided (a local source took the Cluster group)
+# gpc_source (fields.go PktSourceField); "from local" is GATEWAY or POD
+SOURCE_UNKNOWN, SOURCE_TUNNEL, SOURCE_GATEWAY, SOURCE_POD, SOURCE_UPLINK, SOURCE_BRIDGE, SOURCE_TC_RETURN = range(7)
 # gpc_affinity_entry (gpc_debug_affinity_table)
 AFF_ENTRY_DTYPE = np.dtype([("install_id", "<u4"), ("src", "<u4"), ("dst", "<u4"), ("endpoint_ip", "<u4"),
                             ("endpoint_port", "<u4"), ("expires", "<u4")])
@@ -62,7 +65,7 @@ class gpc_config(C.Structure):
                 ("enable_deny_tracking", C.c_int32), ("cookie", C.c_uint64), ("device", C.c_int32),
                 ("compact_after", C.c_int32), ("ovs_meters", C.c_int32), ("external_node", C.c_int32),
                 ("group_packets", C.c_int32), ("group_key", C.c_int32), ("launch_pacing", C.c_int32),
-                ("session_affinity", C.c_int32), ("session_affinity6", C.c_int32)]
+                ("session_affinity", C.c_int32), ("session_affinity6", C.c_int32), ("packet_source", C.c_int32)]
 
 
 class gpc_addr(C.Structure):
@@ -91,7 +94,7 @@ class gpc_rule(C.Structure):
 class gpc_pkt_soa(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("src", "dst", "sport", "dport", "proto", "out_port", "in_port", "svc_group",
                                           "tun_id", "ct_src", "ct_dst", "ct_state", "dest", "len",
-                                          "src6", "dst6", "ct_src6", "ct_dst6", "ct_mark")]
+                                          "src6", "dst6", "ct_src6", "ct_dst6", "ct_mark", "source")]
 
 
 class gpc_pin_queue(C.Structure):
@@ -419,7 +422,8 @@ PKT_COLUMNS = {"src": np.uint32, "dst": np.uint32, "sport": np.uint16, "dport": 
                "out_port": np.uint32, "in_port": np.uint32, "svc_group": np.uint32, "tun_id": np.uint32,
                "ct_src": np.uint32, "ct_dst": np.uint32, "ct_state": np.uint8, "dest": np.uint8, "len": np.uint16,
                # IPv6 batches: (n, 16) uint8, network byte order
-               "src6": np.uint8, "dst6": np.uint8, "ct_src6": np.uint8, "ct_dst6": np.uint8, "ct_mark": np.uint8}
+               "src6": np.uint8, "dst6": np.uint8, "ct_src6": np.uint8, "ct_dst6": np.uint8, "ct_mark": np.uint8,
+               "source": np.uint8}  # gpc_source; read only by a Classifier(packet_source=...) context
 
 
 def pkt_soa_host(cols: Dict[str, np.ndarray]):
@@ -458,7 +462,8 @@ class Classifier:
 
     def __init__(self, ipv4=True, ipv6=False, enable_antrea_policy=True, enable_deny_tracking=False,
                  cookie=0x1020000000000, device=0, compact_after=0, ovs_meters=False, k8s_node=True, group_packets=0,
-                 group_key=0, devices=None, launch_pacing=0, session_affinity=0, session_affinity6=0):
+                 group_key=0, devices=None, launch_pacing=0, session_affinity=0, session_affinity6=0,
+                 packet_source=0):
         self.lib = load()
         cfg = gpc_config(ipv4_enabled=int(ipv4), ipv6_enabled=int(ipv6),
                          enable_antrea_policy=int(enable_antrea_policy),
@@ -466,7 +471,8 @@ class Classifier:
                          compact_after=int(compact_after), ovs_meters=int(ovs_meters),
                          external_node=int(not k8s_node), group_packets=int(group_packets),
                          group_key=int(group_key), launch_pacing=int(launch_pacing),
-                         session_affinity=int(session_affinity), session_affinity6=int(session_affinity6))
+                         session_affinity=int(session_affinity), session_affinity6=int(session_affinity6),
+                         packet_source=int(packet_source))
         h = C.c_void_p()
         if devices is None:
             _check(self.lib.gpc_create(C.byref(cfg), C.byref(h)), "gpc_create")

@@ -249,7 +249,7 @@ VIRTUAL_NODE_PORT_DNAT = "169.254.0.252"                    # config.VirtualNode
 
 def add_services(wl: Workload, n_services: int, eps_per_service: int, seed=RULE_SEED + 4, remote_frac=0.7,
                  noep_frac=0.02, local_policy_frac=0.1, svc_frac=0.5, nodeport_frac=0.0, affinity_frac=0.0,
-                 affinity_timeout=100) -> Workload:
+                 affinity_timeout=100, short_circuit_frac=0.0) -> Workload:
     """ClusterIP Services (10.96.0.0/12) with `eps_per_service` Endpoints each: local Endpoints are
     the workload's local Pods (ofports known to the Pod map), remote ones are Pods on other Nodes
     (10.128.0.0/9). A fraction of Services has no Endpoints, a fraction Local traffic policy.
@@ -259,7 +259,13 @@ def add_services(wl: Workload, n_services: int, eps_per_service: int, seed=RULE_
     of NODE_PORT_ADDRESSES or the virtual IP; wl.node_port_addresses is set.
     `affinity_frac` > 0: that fraction of the Services has sessionAffinity: ClientIP with
     `affinity_timeout` seconds (their configs carry affinity_timeout, their groups are installed with
-    session affinity: wl.affinity_groups); needs a Classifier(session_affinity=...)."""
+    session affinity: wl.affinity_groups); needs a Classifier(session_affinity=...).
+    `short_circuit_frac` > 0: that fraction of the Services is external with externalTrafficPolicy:
+    Local (LoadBalancer IPs, or NodePort Services where nodeport_frac drew one) with both groups
+    installed -- the Cluster group holds every Endpoint, the Local group the local ones (none, when
+    all are remote: external packets are then rejected while local ones are served); gen_packets adds
+    a `source` column mixing POD, GATEWAY, UPLINK and TUNNEL (wl.short_circuit); needs a
+    Classifier(packet_source=...). At 0 nothing is drawn: every seed yields the workload it always did."""
     rng = np.random.default_rng(seed)
     base = int(ipaddress.ip_address("10.96.0.0"))
     ips = base + 1 + rng.choice(1 << 20, size=n_services, replace=False)
@@ -311,6 +317,21 @@ def add_services(wl: Workload, n_services: int, eps_per_service: int, seed=RULE_
             s = wl.services[i]
             s["affinity_timeout"] = int(affinity_timeout)
             wl.affinity_groups.add(s["local_group_id"] if s["traffic_policy_local"] else s["cluster_group_id"])
+    wl.short_circuit = False
+    if short_circuit_frac > 0:  # (a generator of its own, drawn last)
+        srng = np.random.default_rng(seed + 41)
+        for i in np.nonzero(srng.random(n_services) < short_circuit_frac)[0]:
+            s = wl.services[i]
+            cgid, lgid = s["cluster_group_id"], s["local_group_id"]
+            eps = wl.groups.pop(cgid, None)
+            if eps is None:
+                eps = wl.groups.pop(lgid)
+            wl.groups[cgid] = eps
+            wl.groups[lgid] = [e for e in eps if e["is_local"]]
+            s.update(is_external=True, traffic_policy_local=True)
+            if s.get("affinity_timeout"):
+                wl.affinity_groups.update((cgid, lgid))
+        wl.short_circuit = True
     wl.svc_meta = {"ip": ips.astype(np.uint32), "port": ports.astype(np.uint16),
                    "proto": np.array([SVC_PROTOS[k][1] for k in pk], np.uint8)}
     wl.svc_frac = svc_frac
@@ -346,6 +367,9 @@ CONFIGS = {"C1": config1, "C2": config2, "C2g": config2g, "C3": config3, "C4": c
 
 
 # ------------------------------------------------------------------------------------- packets
+PKT_SOURCES = (3, 2, 4, 1)  # gpc_source POD, GATEWAY, UPLINK, TUNNEL: the `source` column of short-circuit workloads
+
+
 def gen_packets(wl: Workload, n: int, seed=PKT_SEED) -> Dict[str, np.ndarray]:
     """SoA packet columns (numpy) for workload `wl` (see module docstring for the mix)."""
     rng = np.random.default_rng(seed)
@@ -387,8 +411,11 @@ def gen_packets(wl: Workload, n: int, seed=PKT_SEED) -> Dict[str, np.ndarray]:
         dport = np.where(to_svc, sm["port"][k], dport).astype(np.uint16)
         proto = np.where(to_svc, sm["proto"][k], proto).astype(np.uint8)
         sport = np.where(to_svc, rng.integers(1024, 65536, size=n), sport).astype(np.uint16)
-    return {"src": src, "dst": dst, "sport": sport, "dport": dport, "proto": proto, "out_port": out_port,
+    cols = {"src": src, "dst": dst, "sport": sport, "dport": dport, "proto": proto, "out_port": out_port,
             "len": length}
+    if getattr(wl, "short_circuit", False):  # gpc_source: Pod, gateway, uplink, tunnel (a generator of its own)
+        cols["source"] = np.array(PKT_SOURCES, np.uint8)[np.random.default_rng(seed + 53).integers(0, len(PKT_SOURCES), size=n)]
+    return cols
 
 
 def gen_packets_torch(wl: Workload, n: int, seed=PKT_SEED, device="cuda"):
@@ -437,8 +464,12 @@ def gen_packets_torch(wl: Workload, n: int, seed=PKT_SEED, device="cuda"):
         dport = torch.where(to_svc, sm["port"][k], dport)
         proto = torch.where(to_svc, sm["proto"][k], proto)
     u32 = lambda t: (t & 0xFFFFFFFF).to(torch.int64).to(torch.uint32) if hasattr(torch, "uint32") else t.to(torch.int32)
-    return {"src": u32(src), "dst": u32(dst), "sport": sport.to(torch.int16), "dport": dport.to(torch.int16),
+    cols = {"src": u32(src), "dst": u32(dst), "sport": sport.to(torch.int16), "dport": dport.to(torch.int16),
             "proto": proto.to(torch.uint8), "out_port": u32(out_port), "len": length.to(torch.int16)}
+    if getattr(wl, "short_circuit", False):  # (drawn last: the other columns are those of the workload without it)
+        pick = torch.randint(0, len(PKT_SOURCES), (n,), generator=g, device=device)
+        cols["source"] = torch.tensor(PKT_SOURCES, dtype=torch.uint8, device=device)[pick]
+    return cols
 
 
 # ------------------------------------------------------------------------------------- IPv6
@@ -569,6 +600,7 @@ def services_to_ipv6(wl: Workload, embed="96") -> Workload:
     out.svc_meta, out.svc_frac = copy.copy(wl.svc_meta), wl.svc_frac
     if getattr(wl, "affinity_groups", None):  # session affinity (the configs carry affinity_timeout over as they are)
         out.affinity_groups = set(wl.affinity_groups)
+    out.short_circuit = getattr(wl, "short_circuit", False)
     return out
 
 

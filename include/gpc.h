@@ -109,6 +109,18 @@ enum gpc_verdict_action {
 
 /* Packet destination class, as IngressSecurityClassifier sees reg0 (fields.go PktDestinationField). */
 enum gpc_dest { GPC_DEST_POD = 0, GPC_DEST_GATEWAY = 1, GPC_DEST_TUNNEL = 2, GPC_DEST_UPLINK = 3 };
+/* Packet source class, as the Classifier table leaves it in reg0[0..3] (fields.go PktSourceField).
+ * "From local" (FromLocalRegMark reg4[28], pipeline.go:540, 557) is GATEWAY or POD; every other
+ * value, values above TC_RETURN included, is not local. */
+enum gpc_source {
+  GPC_SOURCE_UNKNOWN = 0,
+  GPC_SOURCE_TUNNEL = 1,
+  GPC_SOURCE_GATEWAY = 2,
+  GPC_SOURCE_POD = 3,
+  GPC_SOURCE_UPLINK = 4,
+  GPC_SOURCE_BRIDGE = 5,
+  GPC_SOURCE_TC_RETURN = 6
+};
 #define GPC_CT_NEW 0x01
 #define GPC_CT_EST 0x02
 #define GPC_CT_REL 0x04
@@ -153,6 +165,12 @@ typedef struct gpc_config {
                                     table of 2^n entries (64 B each: the key holds the 128-bit client
                                     address) per device slot; anything else fails gpc_create. Independent of
                                     session_affinity; each table is allocated by its first batch that needs it */
+  int32_t packet_source;         /* the caller's batches may carry gpc_pkt_soa.source (appended at the end of the
+                                    struct, as the affinity fields were: the ABI version stays 6): 0 = the
+                                    library never reads that member (a caller compiled against the shorter
+                                    gpc_pkt_soa stays valid) and external Services with externalTrafficPolicy:
+                                    Local are rejected; non-zero = the member is read (NULL: UNKNOWN) and those
+                                    Services are accepted, both families (gpc_install_service_flows)           */
 } gpc_config;
 
 /* Order a grouped batch is classified in, inside every tile of 16384 packets (results never depend
@@ -230,6 +248,8 @@ typedef struct gpc_pkt_soa {
   const uint8_t* ct_src6;        /* ct_ipv6_src */
   const uint8_t* ct_dst6;        /* ct_ipv6_dst */
   const uint8_t* ct_mark;        /* ct_mark[0..7] (0); GPC_CT_MARK_HAIRPIN steers IngressSecurityClassifier */
+  const uint8_t* source;         /* gpc_source (UNKNOWN); read only in a gpc_config.packet_source context: it picks
+                                    the ServiceLB flow of an external Service with externalTrafficPolicy: Local */
 } gpc_pkt_soa;
 
 typedef struct gpc_verdict {     /* 8 bytes; gpc_classify writes 2 per packet: [egress, ingress] */
@@ -280,6 +300,9 @@ typedef struct gpc_lb_result {
 #define GPC_LB_AFFINITY 0x10     /* session affinity: the Endpoint came from a learned entry or from the
                                     packet of this batch that learned it                         */
 #define GPC_LB_LEARNED 0x20      /* ... and this packet created the entry                         */
+#define GPC_LB_SHORT_CIRCUIT 0x40 /* the priority-210 ServiceLB flow decided: a packet from a local Pod or the
+                                    gateway to an external Service with externalTrafficPolicy: Local took the
+                                    Cluster group (gpc_config.packet_source, gpc_pkt_soa.source)              */
 /* The same for an IPv6 packet (optional output of gpc_classify6_lb), 32 bytes, 16-byte aligned. */
 typedef struct gpc_lb_result6 {
   uint8_t endpoint_ip[16];       /* selected Endpoint (xxreg3), network byte order; 0 if none */
@@ -425,8 +448,13 @@ int gpc_install_endpoint_flows(gpc_ctx* ctx, uint8_t protocol, uint8_t family, c
 int gpc_uninstall_endpoint_flows(gpc_ctx* ctx, uint8_t protocol, uint8_t family, const gpc_endpoint* eps, size_t n);
 /* InstallServiceFlows(*types.ServiceConfig) error                           client.go:790
  * Supported: ClusterIP / LoadBalancer / ExternalIP / NodePort Services (optionally Local traffic
- * policy) without DSR, multi-cluster nesting or the external + Local short-circuit; other configs
- * -GPC_EINVAL. Session affinity (affinity_timeout = T > 0): IPv4 configs of a context created with
+ * policy) without DSR or multi-cluster nesting; other configs -GPC_EINVAL. An external Service with
+ * externalTrafficPolicy: Local (is_external && traffic_policy_local) needs a context created with
+ * gpc_config.packet_source (else -GPC_EINVAL): beside the priority-200 flow to the Local group its
+ * short-circuit flow is realized (pipeline.go:2417-2422): priority 210, the same match plus
+ * FromLocalRegMark (reg4[28]), group and reg7 = cluster_group_id, so packets whose
+ * gpc_pkt_soa.source is POD or GATEWAY are served by the Cluster group (GPC_LB_SHORT_CIRCUIT) and
+ * every other packet by the Local group. Both groups must be installed. Session affinity (affinity_timeout = T > 0): IPv4 configs of a context created with
  * gpc_config.session_affinity; the ServiceLB flow then loads EpToLearnRegMark and a priority-190
  * learn flow (serviceLearnFlow, pipeline.go:2316-2371; cookie | TrafficPolicyGroupID) is realized
  * beside it. Its learned flows live in the device's affinity table: keyed by (this install, client
@@ -572,7 +600,13 @@ int gpc_classify(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* o
  * caller that spreads packets over slots must shard by client address. A key that finds no free
  * slot is not learned (gpc_affinity_stats overflow). Two launches (aff_learn, aff_resolve; aff_sweep
  * once per clock value) run in front of the policy launches; without an affinity Service the
- * launches are those of a context without the feature. */
+ * launches are those of a context without the feature.
+ * Packet source (gpc_config.packet_source and a short-circuit Service committed): a packet to such
+ * a Service whose `source` is POD or GATEWAY takes the Service's Cluster group (Endpoint list, hash
+ * modulus, group_id, reg7, NO_ENDPOINT; GPC_LB_SHORT_CIRCUIT), every other packet its Local group.
+ * The affinity key is the same for both; "still belongs to the Service" is judged against the group
+ * the packet's own source selects. The column is loaded only when the batch has it and the bound
+ * Service image holds such a Service; gpc_trace* read it from the host columns under the same gate. */
 int gpc_classify_lb(gpc_ctx* ctx, const gpc_pkt_soa* pkts, size_t n, gpc_verdict* out, gpc_lb_result* lb_out,
                     int32_t count, void* stream);
 /* Traceflow-style readback (traceflow/packetin.go:211-270 reads the verdict registers
